@@ -16,24 +16,29 @@ Started without a launcher (`python bench.py --gpus N`), the script spawns its N
 the parent counts the node's GPUs from the KFD topology in sysfs and never loads the HIP runtime —;
 under `python -m torch.distributed.run` it reads RANK / LOCAL_RANK / WORLD_SIZE from the environment.
 
-The N > 1 line carries its own correctness evidence (`partition_check`: every rank also runs the
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes what the
+last timed step returned (DIR/out.npy; inputs are seeded, so two builds compare output for output).  Everything
+else below is measured only with `--full`.
+
+With `--full` the N > 1 line carries its own correctness evidence (`partition_check`: every rank also runs the
 WHOLE-graph launch once and compares its rows bit for bit with what the partitioned step produced
 through the real collective; the backward against the whole graph's at 1e-5), the GAT partition of
 BASELINE configs[4] in a second, shorter loop (`gat_partition`, with the same check), the
-exchange-free channel partition (`alt_partition`), per-rank device times, the exchange alone and the
-kernels alone (`exchange`), the RCCL version, and the two transports of the exchange as timed
-variants (`comm_variants`: torch.distributed's all_to_all_single | the library's own grouped
-ncclSend/ncclRecv, `stag_halo_exchange_multi`).  Everything after the headline loop is best-effort:
-an exception becomes an `error` string in its object, a watchdog prints the line as far as it
-got if an extra hangs, and if a rank dies hard behind the headline loop (the launcher then tears the
-job down) rank 0's guardian process — forked before rank 0 touches the GPU — prints the last snapshot
-of the line with `extras_crashed`.
+exchange-free channel partition (`alt_partition`), the exchange alone and the kernels alone
+(`exchange`), and the two transports of the exchange as timed variants (`comm_variants`:
+torch.distributed's all_to_all_single | the library's own grouped ncclSend/ncclRecv,
+`stag_halo_exchange_multi`); per-rank device times and the RCCL version are in every N > 1 line.
+Everything after the headline loop is best-effort: an exception becomes an `error` string in its
+object, a watchdog prints the line as far as it got if an extra hangs, and if a rank dies hard
+behind the headline loop (the launcher then tears the job down) rank 0's guardian process — forked
+before rank 0 touches the GPU — prints the last snapshot of the line with `extras_crashed`.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects: `roofline`
-(algorithmic bytes / device time of the op, measured with HIP events on the launch stream, against
-the 8 TB/s HBM peak; `ceilings` = the two limits that bind before HBM does), `cpu_baseline` (the
-oracle's reference-dataflow twin on the host cores; N=1 only; a baseline, not a target), `variants`
-(N=1: the other single-GPU BASELINE configs and forms, each with its own device time and fraction).
+Prints ONE JSON line on rank 0 with `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall
+time of one timed step) and `roofline` (algorithmic bytes / device time of the op, measured with HIP events on the
+launch stream over the same K steps, against the 8 TB/s HBM peak; `ceilings` = the two limits that bind before HBM
+does).  `--full` adds, at N=1, `cold` (the K steps timed before the settle phase), `cpu_baseline` (the oracle's
+reference-dataflow twin on the host cores; a baseline, not a target) and `variants` (the other single-GPU BASELINE
+configs and forms, each with its own device time and fraction); `cpu_baseline` is null without it.
 """
 import argparse
 import glob
@@ -55,6 +60,7 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 GAT_H, GAT_F = 8, 32    # BASELINE configs[4]: 8 heads, hidden 256
 CHECK_OFFSET = 7777     # Philox offset of the launches the partition check compares
+DUMP_BYTES = 32 << 20   # --dump-outputs: the headline's [169343, 128] fp32 output (87 MB) is written as a row sample
 
 
 def parse(argv=None):
@@ -109,7 +115,21 @@ def parse(argv=None):
     ap.add_argument("--rehearse", action="store_true",
                     help="plumbing check without a GPU: ranks, rendezvous (gloo), partition and exchange run on "
                          "CPU tensors, NO kernel is launched; the line carries rehearsal=true and value=null")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: N=1 the cold reading, `variants` and `cpu_baseline`; "
+                         "N>1 `exchange`, `partition_check`, `gat_partition`, `alt_partition` and `comm_variants` "
+                         "(each still subject to its --no-* option). Without it a run sets up, warms up, times the "
+                         "K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/out.npy (float32; "
+                         "a fixed, seeded sample of its rows, listed in DIR/out_rows.npy, when it is larger than "
+                         f"{DUMP_BYTES >> 20} MiB), gathered from every rank")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.rehearse:
+        ap.error("--dump-outputs: a rehearsal launches no kernel, there is no output to write")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------- launcher
@@ -220,6 +240,37 @@ def make_noise(stag_amd, graph, D, kind, offset):
                  "bernoulli": (_lib.NOISE_BERNOULLI, 0.5, None)}[kind]
     return stag_amd.EdgeNoise(graph, D, k, p0, p1, seed=0x5747A6, offset=offset,
                               in_norm=(kind == "bernoulli"))
+
+
+def dump_outputs(out_dir, out, n, row_shape, partition, multi, rank):
+    """--dump-outputs: write the step's output, [n, *row_shape] over all ranks, as out_dir/out.npy (float32) on rank 0.
+    Above DUMP_BYTES only the rows of a fixed sample (seed 0, sorted; out_rows.npy, float64) are written.  N > 1: every
+    rank contributes the sampled rows it owns — a contiguous row range (nodes) or all rows of a contiguous channel range
+    (channels), both in rank order — so the file is the same array a one-GPU run writes."""
+    k = min(n, max(1, DUMP_BYTES // (4 * int(np.prod(row_shape)))))
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    flat = out.detach().reshape(out.shape[0], -1)
+    if multi:
+        import torch.distributed as dist
+        if partition == "nodes":
+            sizes = [None] * dist.get_world_size()
+            dist.all_gather_object(sizes, int(out.shape[0]))
+            lo = sum(sizes[:rank])
+            mine = rows[(rows >= lo) & (rows < lo + out.shape[0])] - lo
+        else:
+            mine = rows
+        local = flat[torch.from_numpy(mine).to(flat.device)].float().cpu().numpy()
+        pieces = [None] * dist.get_world_size()
+        dist.all_gather_object(pieces, local)
+        if rank != 0:
+            return
+        sample = np.concatenate(pieces, axis=0 if partition == "nodes" else 1)
+    else:
+        sample = flat[torch.from_numpy(rows).to(flat.device)].float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "out.npy"), sample.reshape(len(rows), *row_shape))
+    if k < n:
+        np.save(os.path.join(out_dir, "out_rows.npy"), rows.astype(np.float64))
 
 
 def cpu_baseline(src, dst, n, x, kind, budget_s):
@@ -577,9 +628,11 @@ def main():
             "shard": shard, "exchange_only": exchange_only, "kernels_only": kernels_only,
             "local_units": p_loc["n_units"], "remote_units": p_rem["n_units"], "inputs": (x,)}
 
+    last = {}
+
     def timed(step, steps, warmup, per_rank=False):
         """-> (wall seconds, device ms per step), MAX over ranks; barrier + sync both sides.
-        per_rank: also every rank's own device ms per step."""
+        per_rank: also every rank's own device ms per step.  last["out"]: what the last timed step returned."""
         with torch.no_grad():
             for i in range(warmup):
                 step(i)
@@ -597,6 +650,7 @@ def main():
                 ev1.record()
             fence()
             t1 = time.perf_counter()
+        last["out"] = out
         wall = t1 - t0
         dev_ms = ev0.elapsed_time(ev1) / steps if not rehearse else wall / steps * 1e3
         ranks_ms = None
@@ -738,7 +792,7 @@ def main():
     if multi and args.native_comm and not rehearse and parts is not None:
         use_native(parts["shard"], True)
     cold = None
-    if not multi and not rehearse and not args.no_variants:
+    if args.full and not multi and not rehearse and not args.no_variants:
         # the same K steps BEFORE the settle phase: what a short run reads while the card is still raising its
         # clocks — reported beside the headline number, never as it
         cw, cd = timed(step, args.steps, args.warmup)
@@ -759,6 +813,8 @@ def main():
                          "config": {"workload": f"{workload} on the arxiv-shaped CSR, N={n}, E={E}", "parallelism": parallelism,
                                     "partition": partition},
                          "device_ms_per_step": dev_ms, "snapshot": "headline only: rank 0 ended before it had formed the full line"})
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["out"], n, (H, F) if workload == "gat" else (D,), partition, multi, rank)
 
     def variant_loops():
         """Short timed loops over the other single-GPU BASELINE configs and forms, each with its own
@@ -840,7 +896,7 @@ def main():
                                                    stripe_locality=g4.csr.stripe_locality())
         return out
 
-    variants = variant_loops() if (not multi and not rehearse and not args.no_variants) else None
+    variants = variant_loops() if (args.full and not multi and not rehearse and not args.no_variants) else None
 
     # ---------------------------------------------------------------------------- the line, as far as the headline
     line = None
@@ -937,7 +993,7 @@ def main():
 
     if guardian is not None:
         guardian.update(line)            # the headline is safe from here on
-    if multi and parts is not None:
+    if args.full and multi and parts is not None:
         if os.environ.get("STAG_BENCH_CRASH_IN_EXTRAS") == str(rank):      # test hook: a rank that dies hard behind the headline
             time.sleep(2.0)              # (somewhere inside the extras, not in the instant rank 0 is still forming its line)
             os._exit(13)
@@ -1014,7 +1070,7 @@ def main():
             dog.cancel()
 
     if rank == 0:
-        if not multi and not args.no_cpu_baseline and not rehearse and workload == "agg":
+        if args.full and not multi and not args.no_cpu_baseline and not rehearse and workload == "agg":
             line["cpu_baseline"] = cpu_baseline(src, dst, n, x_host.numpy(), args.noise, args.cpu_budget_s)
         if guardian is not None:
             guardian.final(line)

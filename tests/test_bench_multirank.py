@@ -29,7 +29,7 @@ def _line(r):
 
 
 def test_gpus2_self_launch_rehearsal_on_cpu():
-    r = _run(["--gpus", "2", "--rehearse", "--steps", "2", "--warmup", "1"])
+    r = _run(["--gpus", "2", "--rehearse", "--steps", "2", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     line = _line(r)
     assert line["n_gpus"] == 2 and line["rehearsal"] is True and line["value"] is None
@@ -79,21 +79,21 @@ def test_a_failing_rank_is_named_with_its_stderr():
 def test_a_rank_dying_behind_the_headline_does_not_lose_the_line():
     """An extra that takes a rank down hard (os._exit in rank 1 after the headline loop): the launcher stops the job,
     rank 0 dies in its collective — and its guardian process prints the line as far as it got, marked."""
-    r = _run(["--gpus", "2", "--rehearse", "--steps", "2", "--warmup", "1"], env={"STAG_BENCH_CRASH_IN_EXTRAS": "1"})
+    r = _run(["--gpus", "2", "--rehearse", "--steps", "2", "--warmup", "1", "--full"], env={"STAG_BENCH_CRASH_IN_EXTRAS": "1"})
     assert r.returncode != 0 and "rank 1 exited with code 13" in r.stderr
     lines = [json.loads(t) for t in r.stdout.splitlines() if t.startswith("{")]
     assert len(lines) == 1 and lines[0]["n_gpus"] == 2 and "ms_per_step" in lines[0]
     # (rank 0 either died in the collective — the guardian's line — or saw its peer vanish as an exception inside the extra)
     assert "extras_crashed" in lines[0] or "error" in lines[0]["exchange"]
     # ... and a clean run prints exactly one line, without the mark
-    r = _run(["--gpus", "2", "--rehearse", "--steps", "2", "--warmup", "1"])
+    r = _run(["--gpus", "2", "--rehearse", "--steps", "2", "--warmup", "1", "--full"])
     lines = [json.loads(t) for t in r.stdout.splitlines() if t.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1 and "extras_crashed" not in lines[0]
 
 
 def test_a_rank_dying_behind_the_headline_under_torchrun():
     """The same under the driver's launcher: torchrun SIGTERMs rank 0 when rank 1 is gone; the guardian survives it."""
-    r = _torchrun(["--rehearse", "--steps", "2", "--warmup", "1"], env={"STAG_BENCH_CRASH_IN_EXTRAS": "1"})
+    r = _torchrun(["--rehearse", "--steps", "2", "--warmup", "1", "--full"], env={"STAG_BENCH_CRASH_IN_EXTRAS": "1"})
     lines = [json.loads(t) for t in r.stdout.splitlines() if t.startswith("{")]
     assert r.returncode != 0 and len(lines) == 1 and lines[0]["n_gpus"] == 2
     assert "extras_crashed" in lines[0] or "error" in lines[0]["exchange"]
@@ -109,7 +109,7 @@ def test_world_size_mismatch_is_an_error():
 def test_gpus2_real_kernels_two_gloo_ranks_on_one_card():
     """The N = 2 step with real kernels (exchange + overlapped local rows + remote rows), gloo standing in
     for RCCL because two RCCL ranks cannot share a device; timings are meaningless, the plumbing is not."""
-    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
+    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--full"],
              env={"STAG_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = _line(r)
@@ -127,7 +127,7 @@ def test_gpus4_full_size_through_the_real_collective_is_bit_identical():
     the partitioned step produced through the REAL collective — must read bit-identical, forward with and without
     the overlap, for the aggregation (`_ShardAggregate`) and for BASELINE configs[4]'s GAT step (`_ShardGat`), and the
     backward through the transposed exchange within 1e-5 of the whole graph's."""
-    r = _run(["--gpus", "4", "--steps", "5", "--warmup", "2", "--no-alt"], env={"STAG_BENCH_BACKEND": "gloo"}, timeout=1100)
+    r = _run(["--gpus", "4", "--steps", "5", "--warmup", "2", "--no-alt", "--full"], env={"STAG_BENCH_BACKEND": "gloo"}, timeout=1100)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = _line(r)
     assert line["n_gpus"] == 4 and len(line["device_ms_per_step_per_rank"]) == 4 and line["comm"]["backend"] == "gloo"
@@ -152,7 +152,7 @@ def test_the_multi_gpu_code_path_over_rccl_itself_with_one_rank():
     all_gather of the line's float64 and int64 records, the partition checks, the library's own communicator as the second
     transport.  STAG_BENCH_FORCE_DIST=1 runs exactly that path with ONE rank over RCCL: every extra of the line must be
     there without an `error`."""
-    r = _run(["--gpus", "1", "--steps", "5", "--warmup", "2"], env={"STAG_BENCH_FORCE_DIST": "1", "STAG_BENCH_BACKEND": "nccl"},
+    r = _run(["--gpus", "1", "--steps", "5", "--warmup", "2", "--full"], env={"STAG_BENCH_FORCE_DIST": "1", "STAG_BENCH_BACKEND": "nccl"},
              timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = _line(r)
@@ -192,7 +192,7 @@ def test_gpus2_under_torchrun_rehearsal_on_cpu():
 
 @pytest.mark.gpu
 def test_gpus2_under_torchrun_real_kernels():
-    r = _torchrun(["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-alt"], env={"STAG_BENCH_BACKEND": "gloo"})
+    r = _torchrun(["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-alt", "--full"], env={"STAG_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = _line(r)
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["exchange"]["kernels_only_us"] > 0
@@ -200,7 +200,7 @@ def test_gpus2_under_torchrun_real_kernels():
 
 @pytest.mark.gpu
 def test_single_gpu_line_contract():
-    r = _run(["--steps", "20", "--warmup", "5", "--cpu-budget-s", "4"])
+    r = _run(["--steps", "20", "--warmup", "5", "--cpu-budget-s", "4", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     line = _line(r)
     assert line["n_gpus"] == 1 and line["config"]["partition"] == "none" and line["value"] > 1e9
@@ -209,3 +209,93 @@ def test_single_gpu_line_contract():
     assert rf["traffic"] is None or "NOT collected in this run" in rf["traffic_source"]
     assert rf["ceilings"]["gather"]["us"] > 0 and rf["ceilings"]["valu_rng"]["us"] > 0
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["cores"] >= 1
+
+
+def _dump_worker(rank, world, port, tmp, partition):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    import bench
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        n, D = 70001, 128                  # 36 MB of fp32 rows: above the dump's cap, so a sample is written
+        full = torch.from_numpy(np.random.default_rng(3).standard_normal((n, D)).astype(np.float32))
+        if partition == "nodes":           # uneven contiguous row ranges in rank order, as GraphShard cuts them
+            b = [0, 20000, 51234, n][:world] + [n]
+            mine = full[b[rank]:b[rank + 1]]
+        else:                              # contiguous channel ranges in rank order, as ChannelShard cuts them
+            b = [0, 32, 96, D][:world] + [D]
+            mine = full[:, b[rank]:b[rank + 1]]
+        bench.dump_outputs(os.path.join(tmp, partition), mine, n, (D,), partition, True, rank)
+        if rank == 0:
+            bench.dump_outputs(os.path.join(tmp, "one"), full, n, (D,), partition, False, 0)
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("partition", ["nodes", "channels"])
+def test_dump_outputs_gathers_the_one_gpu_sample_from_every_rank(tmp_path, partition):
+    """--dump-outputs: three ranks each holding a block of the output write exactly the file one process holding all of
+    it writes — a fixed sample of rows under the size cap, float32, its row ids beside it."""
+    import socket
+    import numpy as np
+    import torch.multiprocessing as mp
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    mp.spawn(_dump_worker, args=(3, port, str(tmp_path), partition), nprocs=3, join=True)
+    one, got = np.load(tmp_path / "one" / "out.npy"), np.load(tmp_path / partition / "out.npy")
+    rows = np.load(tmp_path / "one" / "out_rows.npy")
+    assert one.dtype == np.float32 and one.shape == (len(rows), 128) and one.nbytes <= 32 << 20
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and rows[-1] < 70001
+    assert np.array_equal(got, one) and np.array_equal(np.load(tmp_path / partition / "out_rows.npy"), rows)
+    full = np.random.default_rng(3).standard_normal((70001, 128)).astype(np.float32)
+    assert np.array_equal(one, full[rows.astype(np.int64)])
+
+
+def test_dump_outputs_needs_a_kernel_and_steps_need_to_be_positive():
+    r = _run(["--rehearse", "--steps", "2", "--warmup", "1", "--dump-outputs", "never_written"])
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not os.path.exists(os.path.join(ROOT, "never_written"))
+    r = _run(["--rehearse", "--steps", "0", "--warmup", "1"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_plain_rehearsal_runs_no_extras():
+    """Without --full a run does what its headline needs and nothing else: no exchange report, no checks."""
+    r = _run(["--gpus", "2", "--rehearse", "--steps", "2", "--warmup", "1"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _line(r)
+    assert line["n_gpus"] == 2 and line["steps"] == 2 and "ms_per_step" in line
+    for key in ("exchange", "partition_check", "gat_partition", "alt_partition", "comm_variants"):
+        assert key not in line, key
+
+
+@pytest.mark.gpu
+def test_plain_single_gpu_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """A plain `--gpus 1` run: no cold reading, variants or CPU baseline; `--dump-outputs` writes the last timed step's
+    output — the same bits as ops.aggregate at that step's Philox offset — and the same file on a second run."""
+    import numpy as np
+    import torch
+    K, W = 7, 3
+    for name in ("a", "b"):
+        r = _run(["--steps", str(K), "--warmup", str(W), "--dump-outputs", str(tmp_path / name)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = _line(r)
+        assert line["steps"] == K and line["warmup"] == W and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+        assert "cold" not in line and "variants" not in line
+    out, rows = np.load(tmp_path / "a" / "out.npy"), np.load(tmp_path / "a" / "out_rows.npy")
+    assert out.dtype == np.float32 and out.shape == (len(rows), 128) and out.nbytes + rows.nbytes <= 64e6
+    assert np.array_equal(out, np.load(tmp_path / "b" / "out.npy"))
+    sys.path.insert(0, ROOT)
+    import bench
+    import stag_amd
+    from stag_amd import ops, synthetic
+    dev = torch.device("cuda:0")
+    src, dst = synthetic.arxiv_like(seed=1)
+    n = synthetic.ARXIV_NODES
+    g = stag_amd.Graph(torch.from_numpy(src), torch.from_numpy(dst), n, device=dev)
+    x = torch.randn(n, 128, generator=torch.Generator().manual_seed(0)).to(dev)
+    ref = ops.aggregate(g, x, bench.make_noise(stag_amd, g, 128, "normal", W + K - 1), seg_len=64)
+    assert np.array_equal(out, ref.cpu().numpy()[rows.astype(np.int64)])

@@ -1037,14 +1037,14 @@ def test_training_monte_carlo_loop_batched_on_the_first_layer(dev, first):
 
 def test_bench_contract_and_smoke(dev):
     """The driver's entry points, run the way the driver runs them: `python bench.py` prints ONE JSON
-    line with the contract's keys (plus `roofline` and `cpu_baseline`), and smoke() passes."""
+    line with the contract's keys (plus `roofline` and, with --full, `cpu_baseline`), and smoke() passes."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "30", "--warmup", "5",
-                        "--cpu-budget-s", "3"], cwd=root, capture_output=True, text=True, timeout=600)
+                        "--cpu-budget-s", "3", "--full"], cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
