@@ -33,6 +33,11 @@
  *       ctr  = { lo32(gpos), chunk | (hi32(gpos) << 20), lo32(offset), hi32(offset) }
  *       key  = { lo32(seed), hi32(seed) }
  *       (r0,r1,r2,r3) = philox4x32_10(ctr, key)      channel k = 4*chunk + j uses r_j
+ *   with chunk = spec.chunk_base + (channel of the call) / 4.  Word 1 holds 20 bits of chunk and 12 of
+ *   hi32(gpos), so a launch that draws must keep 0 <= pos_base, pos_base + n_edges <= 2^44 and
+ *   chunk_base + ceil(Dn / 4) <= 2^20 (STAG_EINVAL otherwise: past them two (edge, channel) pairs would
+ *   share a draw), and must not straddle a 2^32 boundary of gpos (STAG_ENOSYS; stag_csr.nidx).
+ *   seed, offset and offset + *epoch are taken mod 2^64.
  *   f12(r) = the fp32 in [1,2) with mantissa (r & 0x7FFFFF)   (23 random bits, exact)
  *   UNIFORM   u_j = f12(r_j) - 1 in [0,1)                    w = fma(high-low, u_j, low)
  *   BERNOULLI u_j as above                                   w = u_j < probs ? 1 : 0

@@ -20,8 +20,9 @@ namespace {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// n_edges: per-edge arrays (explicit weights, [E, 1 | Dn] parameters) of a graph without edges have no address
-int check_spec(const stag_noise_spec* s, int64_t n_edges = 1) {
+// n_edges: per-edge arrays (explicit weights, [E, 1 | Dn] parameters) of a graph without edges have no address.
+// Dn: the noise width, whose chunks must fit the counter word's chunk field (0: not known here)
+int check_spec(const stag_noise_spec* s, int64_t n_edges = 1, int32_t Dn = 0) {
   if (!s) return STAG_EINVAL;
   if (s->kind < STAG_NOISE_NONE || s->kind > STAG_NOISE_BERNOULLI) return STAG_EINVAL;
   if (s->kind == STAG_NOISE_EXPLICIT && !s->p0 && n_edges > 0) return STAG_EINVAL;
@@ -31,6 +32,7 @@ int check_spec(const stag_noise_spec* s, int64_t n_edges = 1) {
   if (s->p1_log != 0 && (s->p1_log != 1 || s->kind != STAG_NOISE_NORMAL)) return STAG_EINVAL;   // a log-scale is a Normal's
   if (s->p1_log && s->param_mode == STAG_PARAM_PER_CHANNEL) return STAG_ENOSYS;   // exponentiate a [Dn] row yourself
   if (s->kind >= STAG_NOISE_NORMAL) {
+    if (!counter_space_ok(s->pos_base, n_edges, s->chunk_base, ((int64_t)Dn + 3) / 4)) return STAG_EINVAL;
     if (s->param_mode < STAG_PARAM_SCALAR || s->param_mode > STAG_PARAM_PER_EDGE) return STAG_EINVAL;
     const bool per_edge = s->param_mode == STAG_PARAM_PER_EDGE1 || s->param_mode == STAG_PARAM_PER_EDGE;
     if (s->param_mode != STAG_PARAM_SCALAR && !(per_edge && n_edges == 0)) {
@@ -791,7 +793,7 @@ static int agg_common(const stag_csr* csr, const stag_plan* plan, const float* x
                       const EdgeGradOut* eg = nullptr) {
   int rc = check_csr(csr);
   if (rc) return rc;
-  rc = check_spec(spec, csr->n_edges);
+  rc = check_spec(spec, csr->n_edges, D);
   if (rc) return rc;
   if (D <= 0 || (ldx != 0 && ldx < D) || ldo < D) return STAG_EINVAL;
   if (reduce != STAG_REDUCE_SUM && reduce != STAG_REDUCE_MEAN) return STAG_EINVAL;
@@ -1096,7 +1098,7 @@ int stag_noise_materialize(const stag_csr* csr, const stag_plan* plan, const sta
                            int32_t Dn, float* w, int64_t ldw, float* norm_scale, void* stream) {
   int rc = check_csr(csr);
   if (rc) return rc;
-  rc = check_spec(spec, csr->n_edges);
+  rc = check_spec(spec, csr->n_edges, Dn);
   if (rc) return rc;
   if (!w || Dn <= 0 || ldw < Dn) return STAG_EINVAL;
   if (spec->in_norm && !norm_scale) return STAG_EINVAL;   // [n_dst, Dn] scratch for the row factors
@@ -1140,7 +1142,7 @@ int stag_agg_bwd_w(const stag_csr* csr, const stag_plan* plan, const float* x, i
                    void* stream) {
   int rc = check_csr(csr);
   if (rc) return rc;
-  if (spec) { rc = check_spec(spec, csr->n_edges); if (rc) return rc; }
+  if (spec) { rc = check_spec(spec, csr->n_edges, D); if (rc) return rc; }
   if (!x || !g || !dw || D <= 0 || (ldx != 0 && ldx < D) || ldg < D) return STAG_EINVAL;
   if (ldw < (reduce_k ? 1 : D)) return STAG_EINVAL;
   if (dw1 && !(spec && (spec->kind == STAG_NOISE_NORMAL || spec->kind == STAG_NOISE_UNIFORM))) return STAG_EINVAL;

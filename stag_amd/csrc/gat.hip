@@ -1632,6 +1632,16 @@ static int fill_drop(GatArgs& a, const stag_gat_drop* drop) {
 }
 static bool drop_on(const stag_gat_drop* drop) { return drop && drop->keep_prob < 1.0f; }
 
+// The global positions of a launch that draws (edge weights, or an attention-dropout mask): STAG_EINVAL outside what
+// the counter word names (counter_space_ok), STAG_ENOSYS across a 2^32 boundary (the kernels keep pos_hi fixed and
+// add the local position to pos_lo in 32 bits).
+static int check_positions(const stag_noise_spec* spec, int64_t n_edges, int32_t H, bool drawn) {
+  if (!drawn) return STAG_OK;
+  if (!counter_space_ok(spec->pos_base, n_edges, spec->chunk_base, ((int64_t)H + 3) / 4)) return STAG_EINVAL;
+  if (((uint64_t)spec->pos_base & 0xFFFFFFFFull) + (uint64_t)n_edges > (1ull << 32)) return STAG_ENOSYS;
+  return STAG_OK;
+}
+
 extern "C" size_t stag_gat_workspace_bytes(int32_t n_seg, int32_t H, int32_t F) {
   if (n_seg <= 0 || H <= 0 || F <= 0) return 0;
   return (size_t)n_seg * (size_t)((H * F + 2 * H + 3) & ~3) * sizeof(float);   // rows padded to 16 bytes
@@ -1674,8 +1684,8 @@ extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const fl
   a.key.epoch = spec->epoch;
   a.pos_lo = (uint32_t)((uint64_t)spec->pos_base & 0xFFFFFFFFull);
   a.pos_hi = (uint32_t)((uint64_t)spec->pos_base >> 32);
-  if (spec->kind >= STAG_NOISE_NORMAL && (uint64_t)a.pos_lo + (uint64_t)csr->n_edges > (1ull << 32))
-    return STAG_ENOSYS;
+  const int prc = check_positions(spec, csr->n_edges, H, spec->kind >= STAG_NOISE_NORMAL || drop_on(drop));
+  if (prc) return prc;
   a.out = out; a.stats = stats_out;
   if (fill_drop(a, drop)) return STAG_EINVAL;
   const uint64_t ftb = (uint64_t)csr->n_src * (uint64_t)HF * 4u;
@@ -1784,6 +1794,9 @@ static int fill_edge_args(GatArgs& a, const stag_csr* csr, const stag_plan* plan
   a.key.epoch = spec->epoch;
   a.pos_lo = (uint32_t)((uint64_t)spec->pos_base & 0xFFFFFFFFull);
   a.pos_hi = (uint32_t)((uint64_t)spec->pos_base >> 32);
+  // (a caller with attention dropout checks the positions itself, before it launches anything)
+  const int prc = check_positions(spec, csr->n_edges, H, spec->kind >= STAG_NOISE_NORMAL);
+  if (prc) return prc;
   a.stats = const_cast<float*>(stats);
   a.n_units = csr->n_dst;
   if (plan && plan->n_units > 0) {
@@ -1887,8 +1900,8 @@ extern "C" int stag_gat_bwd_two_pass(const stag_csr* csr, const stag_plan* plan,
   if (!csr->indices || !csr_t->indices || !csr_t->nidx || !el || !er || !ft || !stats || !g || !out) return STAG_EINVAL;
   if (!aligned16(ft) || !aligned16(g) || !aligned16(out) || !aligned16(d_ft) || !aligned16(ade_ws)) return STAG_EINVAL;
   if (spec->kind == STAG_NOISE_EXPLICIT && !spec->p0 && csr->n_edges > 0) return STAG_EINVAL;
-  if (spec->kind >= STAG_NOISE_NORMAL && (uint64_t)((uint64_t)spec->pos_base & 0xFFFFFFFFull) + (uint64_t)csr->n_edges > (1ull << 32))
-    return STAG_ENOSYS;
+  const int prc = check_positions(spec, csr->n_edges, H, spec->kind >= STAG_NOISE_NORMAL);
+  if (prc) return prc;
   const int HF = (int)HF64;
   const size_t need = stag_gat_bwd_workspace_bytes(plan->n_seg, plan_t->n_seg, H, F);
   if (need > 0 && (!plan->workspace || plan->workspace_bytes < need)) return STAG_ENOMEM;
@@ -2047,8 +2060,8 @@ static int gat_bwd_impl(const stag_csr* csr, const stag_plan* plan, const stag_c
   if (csr->eid && !csr_t->eid) return STAG_EINVAL;            // edge ids of the transposed positions
   if (!aligned16(ft) || !aligned16(g) || !aligned16(out) || !aligned16(d_ft) || !aligned16(scratch)) return STAG_EINVAL;
   if (spec->kind == STAG_NOISE_EXPLICIT && !spec->p0 && csr->n_edges > 0) return STAG_EINVAL;
-  if (spec->kind >= STAG_NOISE_NORMAL && (uint64_t)((uint64_t)spec->pos_base & 0xFFFFFFFFull) + (uint64_t)csr->n_edges > (1ull << 32))
-    return STAG_ENOSYS;
+  const int prc = check_positions(spec, csr->n_edges, H, spec->kind >= STAG_NOISE_NORMAL || drop_on(drop));
+  if (prc) return prc;
   if (!plan_t->units || !aligned16(plan_t->units)) return STAG_EINVAL;
   if (plan_t->n_seg > 0 && (!plan_t->long_rows || !plan_t->long_seg_ptr)) return STAG_EINVAL;
   const bool fplan = plan && plan->n_units > 0;

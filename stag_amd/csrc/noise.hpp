@@ -34,6 +34,14 @@ __device__ __forceinline__ PhiloxKey resolve_epoch(PhiloxKey k) {
   return k;
 }
 
+// What the counter word can name (include/stag_hip.h, "Noise stream"): word 1 is chunk | hi32(gpos) << 20, so a
+// launch's global positions must lie in [0, 2^44) and its chunks in [0, 2^20); past either, two different
+// (edge, channel) pairs would draw the same noise.  n_chunk = ceil(Dn / 4) chunks from chunk_base on.
+inline bool counter_space_ok(int64_t pos_base, int64_t n_edges, int64_t chunk_base, int64_t n_chunk) {
+  return pos_base >= 0 && n_edges >= 0 && pos_base <= (1ll << 44) - n_edges && chunk_base >= 0 &&
+         chunk_base + n_chunk <= (1ll << 20);
+}
+
 // the key of the stream `d` offsets further on
 __device__ __forceinline__ PhiloxKey key_plus(PhiloxKey k, uint64_t d) {
   const uint64_t o = (((uint64_t)k.o1 << 32) | k.o0) + d;

@@ -163,7 +163,7 @@ class StagLayer(torch.nn.Module):
         if w is None:
             return
         one = copy.copy(w)
-        one.offset = w.offset + int(s) * w.offset_stride
+        one.offset = (w.offset + int(s) * w.offset_stride) & _random._MASK64
         one.n_samples = 1
         self._edge_weight_handle = one
 

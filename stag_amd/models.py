@@ -6,6 +6,7 @@ from typing import List
 import torch
 
 from .likelihoods import CategoricalLikelihood, Likelihood
+from .random import _MASK64
 
 
 def nll_contrastive(q_a, graph, feat):
@@ -79,12 +80,12 @@ class StagModel(torch.nn.Module):
         h1 = h1.unbind(0)       # ONE autograd node for the S slices (S separate selects would each zero-fill [S, N, out])
         first = self.layers[0]
         for s in range(n_samples):
-            gen.offset = base + s * L + first_used
+            gen.offset = (base + s * L + first_used) & _MASK64
             first.mc_select(s)          # the first layer's "last draw" is sample s, as after the loop's s-th pass
             h = h1[s]
             for layer in self.layers[1:]:
                 h = layer(g, h)
-            if gen.offset != base + (s + 1) * L:
+            if gen.offset != (base + (s + 1) * L) & _MASK64:
                 if s == 0:
                     # a layer consumed offsets it does not report (offsets_per_forward): the batched first layer
                     # drew the later samples at the wrong offsets — discard it and run the plain loop, now and
@@ -97,7 +98,7 @@ class StagModel(torch.nn.Module):
                 raise RuntimeError("a layer consumed a different number of noise offsets from one Monte-Carlo "
                                    "sample to the next")
             yield h
-        gen.offset = base + n_samples * L
+        gen.offset = (base + n_samples * L) & _MASK64
 
     def _mc_plan(self, graph, feat, n_samples):
         """(generator, offsets per sample, base offset, offsets of the first layer, [S, N, out] of the first layer,

@@ -13,6 +13,7 @@ import torch
 from . import _lib, _torch_ext
 from .graph import DEFAULT_SEG_LEN
 from .noise import EdgeNoise
+from .random import _MASK64
 
 _REDUCE = {"sum": _lib.REDUCE_SUM, "mean": _lib.REDUCE_MEAN}
 
@@ -1002,7 +1003,7 @@ def aggregate_mc(graph, x, noise, n_samples, offset_stride=1, reduce="sum", src_
     def one(s):
         import copy
         nz = copy.copy(noise)
-        nz.offset = noise.offset + s * offset_stride
+        nz.offset = (noise.offset + s * offset_stride) & _MASK64
         return aggregate(graph, x, nz, reduce=reduce, src_scale=src_scale, dst_scale=dst_scale, seg_len=seg_len,
                          _gathered=_gathered)
     if getattr(graph, "is_shard", False) and not _gathered:

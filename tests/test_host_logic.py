@@ -768,6 +768,58 @@ def test_abi_argument_validation_without_gpu():
     assert lib.stag_philox_raw(0, 0, 0, 4, 0, f, None) == EINVAL
 
 
+@pytest.mark.parametrize("entry", ["stag_agg_fwd", "stag_agg_fwd_mc", "stag_agg_bwd", "stag_agg_bwd_w",
+                                   "stag_noise_materialize", "stag_gat_fwd", "stag_gat_attn", "stag_gat_bwd_edge"])
+def test_counter_space_refusals_without_gpu(entry):
+    """Every entry point that draws noise refuses what the Philox counter word cannot name (include/stag_hip.h,
+    "Noise stream": word 1 = chunk | hi32(gpos) << 20): a position below 0 or at 2^44 and past it, a channel count
+    that overflows the 20-bit chunk field (STAG_EINVAL), and a launch whose positions straddle a 2^32 boundary
+    (STAG_ENOSYS: the kernels keep hi32 fixed and add in 32 bits).  The checks return before any HIP call."""
+    import ctypes as C
+    from stag_amd import _lib
+    lib = _lib.lib()
+    EINVAL, ENOSYS = -22, -38
+    indptr = np.array([0, 1, 2], np.int32)
+    csr = _lib.Csr(2, 2, 2, indptr.ctypes.data, indptr.ctypes.data, None, None)   # never dereferenced
+    f = C.c_void_p(16)                       # a non-null, 16-B aligned dummy "device pointer"
+    D = 8                                    # Dn: two chunks
+
+    def call(pos_base=0, chunk_base=0):
+        s = _lib.NoiseSpec()
+        s.kind, s.p0_scalar, s.p1_scalar = _lib.NOISE_NORMAL, 1.0, 0.5
+        s.pos_base, s.chunk_base = pos_base, chunk_base
+        sp, c = C.byref(s), C.byref(csr)
+        if entry == "stag_agg_fwd":
+            return lib.stag_agg_fwd(c, None, f, D, D, sp, 0, None, None, f, D, None, None)
+        if entry == "stag_agg_fwd_mc":
+            return lib.stag_agg_fwd_mc(c, None, f, D, D, sp, 2, 1, 0, None, None, f, D, 2 * D, None)
+        if entry == "stag_agg_bwd":
+            return lib.stag_agg_bwd(c, None, f, D, D, sp, None, None, f, None, None, D, None)
+        if entry == "stag_agg_bwd_w":
+            s.deriv = 1
+            return lib.stag_agg_bwd_w(c, None, f, D, f, D, D, None, sp, 0, f, None, D, None)
+        if entry == "stag_noise_materialize":
+            return lib.stag_noise_materialize(c, None, sp, D, f, D, None, None)
+        if entry == "stag_gat_fwd":      # H = 2 heads of F = 4
+            return lib.stag_gat_fwd(c, None, f, f, f, 2, 4, 0.2, sp, None, None, f, None, None)
+        if entry == "stag_gat_attn":
+            return lib.stag_gat_attn(c, None, f, f, 2, 0.2, sp, None, f, f, None)
+        return lib.stag_gat_bwd_edge(c, None, f, f, f, f, f, f, 2, 4, 0.2, sp, None, f, None, None, None)
+
+    if entry not in ("stag_agg_bwd_w", "stag_noise_materialize"):          # (these two form gpos in 64 bits)
+        assert call(pos_base=(1 << 32) - 1) == ENOSYS                        # 2 edges straddle 2^32 positions
+        assert call(pos_base=(5 << 32) - 1) == ENOSYS                        # ... any 2^32 boundary
+    assert call(pos_base=1 << 44) == EINVAL                                  # hi32(gpos) needs 13 bits
+    assert call(pos_base=(1 << 44) - 1) == EINVAL                            # the last edge's gpos = 2^44
+    assert call(pos_base=-1) == EINVAL                                       # a negative position
+    assert call(pos_base=-(1 << 40)) == EINVAL
+    if entry.startswith("stag_gat"):
+        assert call(chunk_base=1) == ENOSYS                                  # heads are not channel-sharded
+    else:
+        assert call(chunk_base=(1 << 20) - 1) == EINVAL                      # chunks 2^20 - 1 and 2^20: past the field
+        assert call(chunk_base=1 << 20) == EINVAL
+
+
 def test_hot_kernel_register_budget():
     """The aggregation kernels are occupancy-sensitive (one VGPR over a step costs a wave per SIMD
     and ~15 % of the launch): the compiler's resource report, saved by the Makefile next to the
