@@ -405,6 +405,40 @@ int stag_agg_bwd_edge(const stag_csr* csr_t, const stag_plan* plan_t, const floa
                       const float* row_scale, const float* x, int64_t ldx, float* dx, int64_t ldo,
                       float* dp0_edge, float* dp1_edge, void* stream);
 
+/* ---- the max reducer (DGL's fn.max: GraphSAGE 'pool', stag/zoo/graph_sage.py:90-93), additive in v19 ----------
+ * Messages  m[e, k] = w[e, k] * x[src_e, k]: w = 1 (NONE), an explicit [E, D] weight by edge id (EXPLICIT, row stride
+ * D, optional relu), or the draw of stag_agg_fwd / stag_noise_materialize at the same counters (NORMAL | UNIFORM |
+ * BERNOULLI, any param_mode, optional relu); one fp32 multiply.  No in-norm (STAG_ENOSYS), no group (STAG_ENOSYS).
+ * stag_agg_max_fwd:
+ *     out[v, k] = max_e m[e, k] over the in-edges of v; +0.0 for a row without in-edges
+ *     cnt[v, k] = number of messages that compare equal to out[v, k]          (int32; cnt may be NULL)
+ *   Ties keep the bits of the FIRST maximal message in CSR order (only -0.0 / +0.0 can tell).  A NaN message makes
+ *   out[v, k] NaN (torch.scatter_reduce(amax) semantics, not maxNum) and cnt 0.  Segments of long rows leave
+ *   (max, count) pairs in plan->workspace (>= stag_plan_workspace_bytes(n_seg, 2 * D, 0)), merged in segment order by
+ *   a second launch: out and cnt are bit-identical for every seg_len, unit order (xcd_order) and channel tiling.
+ *   ldx == 0: one broadcast row (update_all(copy_e, max)).  seg_counters are not used.
+ * stag_agg_max_bwd, on the source-major CSR (csr_t.nidx = forward positions, csr_t.eid = edge ids), with the
+ * forward's out and cnt and the incoming gradient g (row stride ldf for all three):
+ *     gq[v, k]      = g[v, k] / cnt[v, k], 0 where cnt is 0 — every maximal message receives an equal share
+ *     dx[u, k]      = sum_{e: src_e = u} w[e, k] * gq[v_e, k] * [m[e, k] == out[v_e, k]]
+ *     dw[e, k]      = x[src_e, k] * gq[v_e, k] * [tie]            (EXPLICIT only, by edge id, row stride ldw)
+ *     dp0_rows[u,k] = sum_{e: src_e = u} dw/dp0[e, k] * gq * [tie] (dp1_rows: dw/dp1; NORMAL | UNIFORM, SCALAR |
+ *                     PER_CHANNEL): dp_i[k] = sum_u x[u, k] dp_i_rows[u, k] is stag_coldot's.
+ *   m is recomputed bit for bit (the draw from its forward counters), sums run in edge order and segment order:
+ *   results are run-to-run bit-identical.  dx, dw, dp may each be NULL (not all).  PER_EDGE1 parameters: STAG_ENOSYS.
+ *   One difference from torch: where a maximum is exactly +-0, torch.scatter_reduce(amax, include_self=False) also
+ *   counts the zero it starts from, so each tied message gets g / (cnt + 1); here it is g / cnt.
+ *   scratch: >= stag_agg_max_bwd_scratch_bytes(csr_t->n_src, D) bytes, 16-byte aligned (out and g / cnt interleaved
+ *   per 4 channels: one 32-byte fetch per edge); plan_t->workspace >= stag_plan_workspace_bytes(n_seg, NO * D, 0),
+ *   NO = 3 with the dp rows, else 1.                                                                              */
+int stag_agg_max_fwd(const stag_csr* csr, const stag_plan* plan, const float* x, int64_t ldx, int32_t D,
+                     const stag_noise_spec* spec, float* out, int64_t ldo, int32_t* cnt, int64_t ldc, void* stream);
+size_t stag_agg_max_bwd_scratch_bytes(int32_t n_dst, int32_t D);
+int stag_agg_max_bwd(const stag_csr* csr_t, const stag_plan* plan_t, const float* x, int64_t ldx, const float* out,
+                     const int32_t* cnt, const float* g, int64_t ldf, int32_t D, const stag_noise_spec* spec,
+                     float* dx, float* dw, int64_t ldw, float* dp0_rows, float* dp1_rows, int64_t ldd,
+                     void* scratch, size_t scratch_bytes, void* stream);
+
 /* w[eid, k] for every edge of the shard: what the reference keeps in
  * `self._edge_weight_sample` (stag/layers.py:107). relu and in_norm applied.
  * plan (may be NULL): the units bound what one team walks, so a hub row does not serialise.

@@ -199,6 +199,12 @@ def bind(path):
     l.stag_gat_bwd_stages.argtypes = [C.POINTER(Csr), C.POINTER(Plan), C.POINTER(Csr), C.POINTER(Plan), _vp, _vp, _vp,
                                       _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_float, C.POINTER(NoiseSpec), _vp,
                                       C.POINTER(GatDrop), _vp, _vp, _vp, _vp, C.c_int32, _vp]
+    l.stag_agg_max_fwd.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, C.c_int64, C.c_int32, C.POINTER(NoiseSpec),
+                                   _vp, C.c_int64, _vp, C.c_int64, _vp]
+    l.stag_agg_max_bwd_scratch_bytes.restype = C.c_size_t
+    l.stag_agg_max_bwd_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    l.stag_agg_max_bwd.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_int32,
+                                   C.POINTER(NoiseSpec), _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, C.c_size_t, _vp]
     if l.stag_abi_version() != 19:
         raise StagHipError("libstag_hip.so ABI version mismatch")
     return l

@@ -8,6 +8,7 @@
 
 #include "../../include/stag_hip.h"
 #include "agg_kernel.hpp"
+#include "agg_max.hpp"
 
 using namespace stag;
 
@@ -1248,6 +1249,105 @@ int stag_coldot(const float* x, int64_t ldx, const float* t0, const float* t1, i
   else     hipLaunchKernelGGL((coldot_partial_kernel<1>), grid, dim3(256), 0, s, x, ldx, t0, t1, ldt, n_rows, D, cw, part);
   hipLaunchKernelGGL(coldot_final_kernel, dim3((D + 15) / 16), dim3(256), 0, s, part, nb, D, out0, out1);
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
+}
+
+// ---- the max reducer (agg_max.hip) ------------------------------------------------------------------------------
+}  // extern "C" (reopened below)
+namespace {
+// the fields a max launch shares between its two directions; STAG_OK or the code to return
+int max_common(const stag_csr* csr, const stag_plan* plan, const float* x, int64_t ldx, int32_t D,
+               const stag_noise_spec* spec, int32_t nws, MaxArgs& a, int32_t& n_seg) {
+  int rc = check_csr(csr);
+  if (rc) return rc;
+  rc = check_spec(spec, csr->n_edges, D);
+  if (rc) return rc;
+  if (D <= 0 || (ldx != 0 && ldx < D) || ldx < 0) return STAG_EINVAL;
+  if (spec->deriv) return STAG_EINVAL;
+  if (spec->in_norm) return STAG_ENOSYS;                                   // (the composed route keeps it)
+  if (spec->kind == STAG_NOISE_EXPLICIT && spec->group > 1) return STAG_ENOSYS;
+  if (csr->n_edges > 0 && !x) return STAG_EINVAL;
+  const bool logs = spec->kind == STAG_NOISE_NORMAL && spec->p1_log;
+  a = MaxArgs{};
+  a.indptr = csr->indptr; a.indices = csr->indices; a.eid = csr->eid; a.nidx = csr->nidx;
+  a.n_rows = csr->n_dst; a.D = D; a.x = x; a.ldx = ldx;
+  a.kind = spec->kind;
+  a.pmode = spec->kind >= STAG_NOISE_NORMAL ? spec->param_mode : 0;
+  a.nflags = (spec->relu ? kFlagRelu : 0) | (logs ? kFlagLogScale : 0);
+  a.p0 = spec->p0; a.p1 = spec->p1; a.p0s = spec->p0_scalar; a.p1s = logs ? expf(spec->p1_scalar) : spec->p1_scalar;
+  a.key = make_key(spec); a.pos_base = spec->pos_base; a.chunk_base = (uint32_t)spec->chunk_base;
+  if (spec->kind >= STAG_NOISE_NORMAL && ((uint64_t)spec->pos_base & 0xFFFFFFFFull) + (uint64_t)csr->n_edges > (1ull << 32))
+    return STAG_ENOSYS;                                                    // as stag_agg_fwd: one 2^32 range per call
+  a.n_units = csr->n_dst;
+  n_seg = 0;
+  if (plan && plan->n_units > 0) {
+    if (!plan->units || !aligned16(plan->units) || plan->n_seg < 0 || plan->n_long < 0) return STAG_EINVAL;
+    a.units = plan->units; a.n_units = plan->n_units;
+    if (plan->xcd_order) {
+      const int64_t sh = plan->xcd_stride_heavy, sl = plan->xcd_stride_light;
+      if (!aligned16(plan->xcd_order) || sh < 0 || sl < 0 || sh > plan->n_heavy || sl > plan->n_units ||
+          STAG_XCD_STRIPES * (sh + sl) < plan->n_units || STAG_XCD_STRIPES * (sh + sl) > 0x7FFFFFFFll) return STAG_EINVAL;
+      a.units = reinterpret_cast<const stag_unit*>(plan->xcd_order + STAG_XCD_HEADER);
+      a.xcd = 1; a.sh = (int32_t)sh; a.sl = (int32_t)sl;
+    }
+    if (plan->n_seg > 0) {
+      if (!plan->long_rows || !plan->long_seg_ptr || !plan->workspace) return STAG_EINVAL;
+      if (plan->workspace_bytes < stag_plan_workspace_bytes(plan->n_seg, nws * D, 0)) return STAG_ENOMEM;
+      a.long_rows = plan->long_rows; a.long_seg_ptr = plan->long_seg_ptr; a.n_long = plan->n_long;
+      a.ws = plan->workspace; a.nws = nws;
+      n_seg = plan->n_seg;
+    }
+  }
+  return STAG_OK;
+}
+}  // namespace
+extern "C" {
+
+int stag_agg_max_fwd(const stag_csr* csr, const stag_plan* plan, const float* x, int64_t ldx, int32_t D,
+                     const stag_noise_spec* spec, float* out, int64_t ldo, int32_t* cnt, int64_t ldc, void* stream) {
+  if (!out || ldo < D || (cnt && ldc < D)) return STAG_EINVAL;
+  MaxArgs a;
+  int32_t n_seg = 0;
+  const int rc = max_common(csr, plan, x, ldx, D, spec, 2, a, n_seg);
+  if (rc) return rc;
+  if (csr->n_dst == 0) return STAG_OK;
+  a.out = out; a.ldo = ldo; a.cnt = cnt; a.ldc = ldc;
+  return max_fwd_launch(a, n_seg, (hipStream_t)stream) == hipSuccess ? STAG_OK : STAG_EIO;
+}
+
+size_t stag_agg_max_bwd_scratch_bytes(int32_t n_dst, int32_t D) {
+  if (n_dst <= 0 || D <= 0) return 0;
+  return (size_t)n_dst * (size_t)((D + 3) / 4) * 8u * sizeof(float);
+}
+
+int stag_agg_max_bwd(const stag_csr* csr_t, const stag_plan* plan_t, const float* x, int64_t ldx, const float* out,
+                     const int32_t* cnt, const float* g, int64_t ldf, int32_t D, const stag_noise_spec* spec,
+                     float* dx, float* dw, int64_t ldw, float* dp0_rows, float* dp1_rows, int64_t ldd,
+                     void* scratch, size_t scratch_bytes, void* stream) {
+  if (!spec || !csr_t) return STAG_EINVAL;
+  if ((dp0_rows == nullptr) != (dp1_rows == nullptr)) return STAG_EINVAL;
+  if (!dx && !dw && !dp0_rows) return STAG_EINVAL;                      // nothing asked for
+  if ((dx || dp0_rows) && ldd < D) return STAG_EINVAL;
+  if (dx && ldx == 0) return STAG_EINVAL;                               // a broadcast row has no rows to differentiate
+  if (dw && (spec->kind != STAG_NOISE_EXPLICIT || ldw < D)) return STAG_EINVAL;
+  if (dw && spec->relu) return STAG_ENOSYS;
+  if (dp0_rows) {
+    if (spec->kind != STAG_NOISE_NORMAL && spec->kind != STAG_NOISE_UNIFORM) return STAG_EINVAL;
+    if (spec->param_mode != STAG_PARAM_SCALAR && spec->param_mode != STAG_PARAM_PER_CHANNEL) return STAG_EINVAL;
+  }
+  if (spec->kind >= STAG_NOISE_NORMAL && spec->param_mode == STAG_PARAM_PER_EDGE1) return STAG_ENOSYS;
+  MaxArgs a;
+  int32_t n_seg = 0;
+  int rc = max_common(csr_t, plan_t, x, ldx, D, spec, dp0_rows ? 3 : 1, a, n_seg);
+  if (rc) return rc;
+  if (csr_t->n_edges > 0 && spec->kind >= STAG_NOISE_NORMAL && !csr_t->nidx) return STAG_EINVAL;   // the FORWARD's draw
+  if (csr_t->n_src > 0 && (!out || !cnt || !g || ldf < D)) return STAG_EINVAL;
+  if (csr_t->n_dst == 0) return STAG_OK;
+  if (csr_t->n_src > 0 && (!scratch || !aligned16(scratch))) return STAG_EINVAL;
+  if (scratch_bytes < stag_agg_max_bwd_scratch_bytes(csr_t->n_src, D)) return STAG_ENOMEM;
+  a.out_in = out; a.cnt_in = cnt; a.g = g; a.ldf = ldf;
+  a.og = static_cast<float*>(scratch); a.n_og_rows = csr_t->n_src;
+  a.dx = dx; a.dp0 = dp0_rows; a.dp1 = dp1_rows; a.ldd = ldd; a.dw = dw; a.ldw = ldw;
+  return max_bwd_launch(a, n_seg, (hipStream_t)stream) == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // torch_ext.cpp — PyTorch-ROCm front end of the hot calls: TORCH_LIBRARY ops `stag::agg_fwd`, `stag::agg_bwd` and (round 4)
-// `stag::agg_fwd_mc`, `stag::agg_bwd_dp`, `stag::gat_fwd`, `stag::gat_bwd` over the C ABI of include/stag_hip.h (the boundary stays that header; this file only
+// `stag::agg_fwd_mc`, `stag::agg_bwd_dp`, `stag::gat_fwd`, `stag::gat_bwd`, `stag::agg_max_fwd`, `stag::agg_max_bwd` over the C ABI of include/stag_hip.h (the boundary stays that header; this file only
 // marshals tensors into its structs, allocates outputs with the caching allocator and picks the current
 // HIP stream).  Replaces the ctypes marshalling on the per-layer path (stag_amd/ops.py falls back to ctypes
 // when this module is not built); the ops are visible to the dispatcher and carry Meta kernels, so a
@@ -241,6 +241,78 @@ std::tuple<Tensor, Tensor, Tensor> agg_bwd_dp_meta(const Tensor& indptr, const T
           at::empty({D}, g_in.options())};
 }
 
+// the max reducer (stag_agg_max_fwd; DGL's fn.max, stag/zoo/graph_sage.py:90-93): out [M, D] and, when a backward
+// can follow, the tie counts [M, D] int32 (else an empty tensor)
+std::tuple<Tensor, Tensor> agg_max_fwd(const Tensor& indptr, const Tensor& indices, OptT eid, OptT nidx, int64_t n_src,
+                                       OptT units, OptT long_rows, OptT long_seg_ptr, OptT block_ptr, OptT xcd,
+                                       OptT counters, at::IntArrayRef plan_ints, const Tensor& x, bool broadcast_x,
+                                       at::IntArrayRef noise_ints, at::IntArrayRef noise_u64,
+                                       at::ArrayRef<double> noise_floats, OptT p0, OptT p1, OptT epoch, bool want_cnt) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.stride(-1) == 1, "x: fp32 rows on the device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Graph g = make_graph(indptr, indices, eid, nidx, n_src, units, long_rows, long_seg_ptr, block_ptr, xcd, counters, plan_ints);
+  const stag_noise_spec spec = make_spec(noise_ints, noise_u64, noise_floats, p0, p1, epoch);
+  const int64_t D = broadcast_x ? x.numel() : x.size(1), n = g.csr.n_dst;
+  Tensor out = at::empty({n, D}, x.options());
+  Tensor cnt = at::empty({want_cnt ? n : 0, D}, x.options().dtype(at::kInt));
+  if (n == 0) return {out, cnt};
+  Tensor ws;
+  give_workspace(g, g.has_plan ? stag_plan_workspace_bytes(g.plan.n_seg, (int32_t)(2 * D), 0) : 0, x, ws);
+  check_rc(stag_agg_max_fwd(&g.csr, g.has_plan ? &g.plan : nullptr, x.data_ptr<float>(), broadcast_x ? 0 : x.stride(0),
+                            (int32_t)D, &spec, out.data_ptr<float>(), D, want_cnt ? cnt.data_ptr<int32_t>() : nullptr, D,
+                            stream_of(x)),
+           "stag_agg_max_fwd");
+  return {out, cnt};
+}
+
+std::tuple<Tensor, Tensor> agg_max_fwd_meta(const Tensor& indptr, const Tensor&, OptT, OptT, int64_t, OptT, OptT, OptT, OptT,
+                                            OptT, OptT, at::IntArrayRef, const Tensor& x, bool broadcast_x, at::IntArrayRef,
+                                            at::IntArrayRef, at::ArrayRef<double>, OptT, OptT, OptT, bool want_cnt) {
+  const int64_t D = broadcast_x ? x.numel() : x.size(1), n = indptr.numel() - 1;
+  return {at::empty({n, D}, x.options()), at::empty({want_cnt ? n : 0, D}, x.options().dtype(at::kInt))};
+}
+
+// its backward on the source-major CSR (stag_agg_max_bwd): dx [n_dst_t, D], dw [E, D] (explicit weights), and the two
+// parameter-derivative aggregates [n_dst_t, D]; what is not asked for comes back empty
+std::tuple<Tensor, Tensor, Tensor, Tensor> agg_max_bwd(
+    const Tensor& indptr, const Tensor& indices, OptT eid, OptT nidx, int64_t n_src, OptT units, OptT long_rows,
+    OptT long_seg_ptr, OptT block_ptr, OptT xcd, OptT counters, at::IntArrayRef plan_ints, const Tensor& x, bool broadcast_x,
+    const Tensor& out, const Tensor& cnt, const Tensor& g_in, at::IntArrayRef noise_ints, at::IntArrayRef noise_u64,
+    at::ArrayRef<double> noise_floats, OptT p0, OptT p1, OptT epoch, bool want_dx, bool want_dw, bool want_dp) {
+  TORCH_CHECK(g_in.is_cuda() && g_in.scalar_type() == at::kFloat && g_in.is_contiguous() && g_in.dim() == 2, "g: [M, D] fp32");
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.is_contiguous() && out.sizes() == g_in.sizes(), "out: like g");
+  TORCH_CHECK(cnt.scalar_type() == at::kInt && cnt.is_contiguous() && cnt.sizes() == g_in.sizes(), "cnt: int32, like g");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.stride(-1) == 1, "x: fp32 rows");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(g_in.device());
+  Graph g = make_graph(indptr, indices, eid, nidx, n_src, units, long_rows, long_seg_ptr, block_ptr, xcd, counters, plan_ints);
+  const stag_noise_spec spec = make_spec(noise_ints, noise_u64, noise_floats, p0, p1, epoch);
+  const int64_t D = g_in.size(1), n = g.csr.n_dst, E = g.csr.n_edges;
+  Tensor dx = at::empty({want_dx ? n : 0, D}, g_in.options());
+  Tensor dw = at::empty({want_dw ? E : 0, D}, g_in.options());
+  Tensor t0 = at::empty({want_dp ? n : 0, D}, g_in.options()), t1 = at::empty({want_dp ? n : 0, D}, g_in.options());
+  if (n == 0) return {dx, dw, t0, t1};
+  Tensor ws;
+  give_workspace(g, g.has_plan ? stag_plan_workspace_bytes(g.plan.n_seg, (int32_t)((want_dp ? 3 : 1) * D), 0) : 0, g_in, ws);
+  const size_t sbytes = stag_agg_max_bwd_scratch_bytes(g.csr.n_src, (int32_t)D);
+  Tensor scratch = at::empty({(int64_t)(sbytes / 4 + 4)}, g_in.options());
+  check_rc(stag_agg_max_bwd(&g.csr, g.has_plan ? &g.plan : nullptr, x.data_ptr<float>(), broadcast_x ? 0 : x.stride(0),
+                            out.data_ptr<float>(), cnt.data_ptr<int32_t>(), g_in.data_ptr<float>(), D, (int32_t)D, &spec,
+                            want_dx ? dx.data_ptr<float>() : nullptr, want_dw ? dw.data_ptr<float>() : nullptr, D,
+                            want_dp ? t0.data_ptr<float>() : nullptr, want_dp ? t1.data_ptr<float>() : nullptr, D,
+                            scratch.data_ptr<float>(), sbytes, stream_of(g_in)),
+           "stag_agg_max_bwd");
+  return {dx, dw, t0, t1};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> agg_max_bwd_meta(
+    const Tensor& indptr, const Tensor& indices, OptT, OptT, int64_t, OptT, OptT, OptT, OptT, OptT, OptT, at::IntArrayRef,
+    const Tensor&, bool, const Tensor&, const Tensor&, const Tensor& g_in, at::IntArrayRef, at::IntArrayRef,
+    at::ArrayRef<double>, OptT, OptT, OptT, bool want_dx, bool want_dw, bool want_dp) {
+  const int64_t D = g_in.size(1), n = indptr.numel() - 1, E = indices.numel();
+  return {at::empty({want_dx ? n : 0, D}, g_in.options()), at::empty({want_dw ? E : 0, D}, g_in.options()),
+          at::empty({want_dp ? n : 0, D}, g_in.options()), at::empty({want_dp ? n : 0, D}, g_in.options())};
+}
+
 // attention dropout inside the GAT kernels: drop_floats = [keep_prob] (empty: none), drop_u64 = [seed, offset]
 bool make_drop(stag_gat_drop& d, at::ArrayRef<double> drop_floats, at::IntArrayRef drop_u64, OptT drop_epoch) {
   if (drop_floats.empty()) return false;
@@ -361,6 +433,9 @@ TORCH_LIBRARY(stag, m) {
         "int n_samples, int offset_stride, int reduce, Tensor? src_scale, Tensor? dst_scale) -> Tensor");
   m.def("agg_bwd_dp(" STAG_GRAPH_ARGS "Tensor g, Tensor? x, " STAG_NOISE_ARGS
         "Tensor? g_scale, Tensor? row_scale, bool want_dx) -> (Tensor, Tensor, Tensor)");
+  m.def("agg_max_fwd(" STAG_GRAPH_ARGS "Tensor x, bool broadcast_x, " STAG_NOISE_ARGS "bool want_cnt) -> (Tensor, Tensor)");
+  m.def("agg_max_bwd(" STAG_GRAPH_ARGS "Tensor x, bool broadcast_x, Tensor out, Tensor cnt, Tensor g, " STAG_NOISE_ARGS
+        "bool want_dx, bool want_dw, bool want_dp) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("gat_fwd(" STAG_GRAPH_ARGS "Tensor el, Tensor er, Tensor ft, float neg_slope, " STAG_NOISE_ARGS
         "Tensor? norm_scale, float[] drop_floats, int[] drop_u64, Tensor? drop_epoch, bool want_stats) -> (Tensor, Tensor)");
   m.def("gat_bwd(" STAG_GRAPH_ARGS "Tensor indptr_t, Tensor indices_t, Tensor? eid_t, Tensor? nidx_t, Tensor? units_t, "
@@ -375,6 +450,8 @@ TORCH_LIBRARY_IMPL(stag, CUDA, m) {      // the HIP backend answers to the CUDA 
   m.impl("agg_bwd", &agg_bwd);
   m.impl("agg_fwd_mc", &agg_fwd_mc);
   m.impl("agg_bwd_dp", &agg_bwd_dp);
+  m.impl("agg_max_fwd", &agg_max_fwd);
+  m.impl("agg_max_bwd", &agg_max_bwd);
   m.impl("gat_fwd", &gat_fwd);
   m.impl("gat_bwd", &gat_bwd);
 }
@@ -384,6 +461,8 @@ TORCH_LIBRARY_IMPL(stag, Meta, m) {
   m.impl("agg_bwd", &agg_bwd_meta);
   m.impl("agg_fwd_mc", &agg_fwd_mc_meta);
   m.impl("agg_bwd_dp", &agg_bwd_dp_meta);
+  m.impl("agg_max_fwd", &agg_max_fwd_meta);
+  m.impl("agg_max_bwd", &agg_max_bwd_meta);
   m.impl("gat_fwd", &gat_fwd_meta);
   m.impl("gat_bwd", &gat_bwd_meta);
 }

@@ -653,7 +653,7 @@ class Graph:
 
     # ---- message passing --------------------------------------------------------
     def update_all(self, message_func, reduce_func):
-        """`update_all(u_mul_e | copy_u | copy_e, sum | mean)` on the HIP path.
+        """`update_all(u_mul_e | copy_u | copy_e, sum | mean | max)` on the HIP path.
 
         This is the call the reference's zoo layers make (stag/zoo/gcn.py:94-96,
         stag/zoo/graph_sage.py:71-73, stag/layers.py:12-15)."""
@@ -662,12 +662,24 @@ class Graph:
         if not isinstance(message_func, fn.Message) or not isinstance(reduce_func, fn.Reduce):
             raise TypeError("update_all takes stag_amd.function builtins")
         kind = message_func.kind
-        if reduce_func.kind == "max":          # composed, not fused (ops.aggregate_max)
-            if kind not in ("copy_u", "u_mul_e"):
+        if reduce_func.kind == "max":          # ops.aggregate_max: the fused max reducer on the GPU
+            if kind not in ("copy_u", "u_mul_e", "copy_e"):
                 raise NotImplementedError(f"update_all max with message {kind}")
+            if kind == "copy_e":               # max of edge data: gather a broadcast row of ones, as the sum path does
+                w = self.edata[message_func.fields[0]]
+                shape = w.shape
+                w2 = w.reshape(shape[0], -1)
+                ones = torch.ones(1, w2.shape[1], dtype=w2.dtype, device=w2.device)
+                out = ops.aggregate_max(self, ones, w2, _broadcast_x=True)
+                self.dstdata[reduce_func.out] = out.reshape((self._n,) + tuple(shape[1:]))
+                return
             x = self.srcdata[message_func.fields[0]]
             w = self.edata[message_func.fields[1]] if kind == "u_mul_e" else None
             if torch.is_tensor(w):
+                if tuple(w.shape[1:]) != tuple(x.shape[1:]):   # DGL broadcasting, e.g. [E,H,1] x [N,H,F]
+                    while w.dim() < x.dim():
+                        w = w.unsqueeze(-1)
+                    w = w.expand((w.shape[0],) + tuple(x.shape[1:]))
                 w = w.reshape(w.shape[0], -1)
             out = ops.aggregate_max(self, x.reshape(x.shape[0], -1), w)
             self.dstdata[reduce_func.out] = out.reshape((self._n,) + tuple(x.shape[1:]))

@@ -971,12 +971,177 @@ def aggregate(graph, x, weight=None, reduce="sum", src_scale=None, dst_scale=Non
                             _f32c(dst_scale), seg_len, _broadcast_x)
 
 
-def aggregate_max(graph, x, weight=None):
+# ---- the max reducer (DGL's fn.max; GraphSAGE 'pool', stag/zoo/graph_sage.py:90-93) --------------------------------
+FUSED_MAX = True          # stag_agg_max_fwd / _bwd | the composed route (messages formed, scatter-amax): tests compare both
+
+
+def _max_fwd_raw(csrv, x, D, spec, seg_len, want_cnt, broadcast_x=False):
+    """One stag_agg_max_fwd on csrv: (out [n_dst, D], cnt [n_dst, D] int32 or None)."""
+    dev = _lib.require_device(x, csrv.indptr)
+    drawn = (spec[0][0] if isinstance(spec, tuple) else spec.kind) >= _lib.NOISE_NORMAL
+    plan_t = csrv.plan(seg_len)
+    if isinstance(spec, tuple):
+        out, cnt = torch.ops.stag.agg_max_fwd(*csrv.torch_args(), *_plan_args(csrv, plan_t, (D + 255) // 256, dev, width=D,
+                                                                               drawn=drawn),
+                                              x, broadcast_x, *spec, bool(want_cnt))
+        return out, (cnt if want_cnt else None)
+    out = torch.empty((csrv.n_dst, D), dtype=torch.float32, device=dev)
+    cnt = torch.empty((csrv.n_dst, D), dtype=torch.int32, device=dev) if want_cnt else None
+    if csrv.n_dst == 0:
+        return out, cnt
+    nbytes = _lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], 2 * D, 0) if plan_t is not None else 0
+    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t, width=D, drawn=drawn)
+    cs = csrv.struct()
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_agg_max_fwd(C.byref(cs), C.byref(plan_c) if plan_c is not None else None, _lib.ptr(x),
+                                         0 if broadcast_x else x.stride(0), D, C.byref(spec), _lib.ptr(out), D,
+                                         _lib.ptr(cnt), D, _lib.stream_of(dev))
+    _lib.check(rc, "stag_agg_max_fwd")
+    return out, cnt
+
+
+def _max_bwd_raw(csrv_t, x, out, cnt, g, D, spec, seg_len, want_dx, want_dw, want_dp, broadcast_x=False):
+    """One stag_agg_max_bwd on the source-major CSR: (dx, dw, dp0_rows, dp1_rows), None where not wanted."""
+    dev = _lib.require_device(x, out, g, csrv_t.indptr)
+    drawn = (spec[0][0] if isinstance(spec, tuple) else spec.kind) >= _lib.NOISE_NORMAL
+    plan_t = csrv_t.plan(seg_len)
+    if isinstance(spec, tuple):
+        dx, dw, t0, t1 = torch.ops.stag.agg_max_bwd(
+            *csrv_t.torch_args(), *_plan_args(csrv_t, plan_t, (D + 255) // 256, dev, width=D, drawn=drawn), x, broadcast_x,
+            out, cnt, g, *spec, bool(want_dx), bool(want_dw), bool(want_dp))
+        return (dx if want_dx else None), (dw if want_dw else None), (t0 if want_dp else None), (t1 if want_dp else None)
+    n = csrv_t.n_dst
+    dx = torch.empty((n, D), dtype=torch.float32, device=dev) if want_dx else None
+    dw = torch.empty((csrv_t.n_edges, D), dtype=torch.float32, device=dev) if want_dw else None
+    t0 = torch.empty((n, D), dtype=torch.float32, device=dev) if want_dp else None
+    t1 = torch.empty((n, D), dtype=torch.float32, device=dev) if want_dp else None
+    if n == 0:
+        return dx, dw, t0, t1
+    nbytes = (_lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], (3 if want_dp else 1) * D, 0)
+              if plan_t is not None else 0)
+    plan_c, _keep = _plan_struct(csrv_t, seg_len, (D + 255) // 256, nbytes, dev, plan_t, width=D, drawn=drawn)
+    sbytes = _lib.lib().stag_agg_max_bwd_scratch_bytes(csrv_t.n_src, D)
+    scratch = torch.empty(sbytes // 4 + 4, dtype=torch.float32, device=dev)
+    cs = csrv_t.struct()
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_agg_max_bwd(
+            C.byref(cs), C.byref(plan_c) if plan_c is not None else None, _lib.ptr(x), 0 if broadcast_x else x.stride(0),
+            _lib.ptr(out), _lib.ptr(cnt), _lib.ptr(g), D, D, C.byref(spec), _lib.ptr(dx), _lib.ptr(dw), D,
+            _lib.ptr(t0), _lib.ptr(t1), D, _lib.ptr(scratch), sbytes, _lib.stream_of(dev))
+    _lib.check(rc, "stag_agg_max_bwd")
+    return dx, dw, t0, t1
+
+
+class _AggregateMax(torch.autograd.Function):
+    """out[v,:] = max over the in-edges of w[e,:] * x[u,:] in one pass (stag_agg_max_fwd); nothing [E, D]-sized is
+    formed or saved.  The backward (stag_agg_max_bwd) walks the source-major CSR, redraws w from its counters and sends
+    g / cnt to every message equal to the maximum; dx, dw (explicit weights) and the parameter gradients of a live
+    Normal / Uniform draw (vi=True; scalar | per-channel) come from that one pass, the latter finished by coldot."""
+
+    @staticmethod
+    def forward(ctx, x, w, p0, p1, graph, noise, seg_len, broadcast_x):
+        x = _f32c(x)
+        D = x.numel() if broadcast_x else x.shape[1]
+        if noise is not None:
+            spec = _noise_spec(noise)
+        elif w is not None:
+            w = _f32c(w)
+            spec = _explicit_spec(w)
+        else:
+            spec = _none_spec()
+        out, cnt = _max_fwd_raw(graph.csr, x, D, spec, seg_len, True, broadcast_x)
+        ctx.graph, ctx.noise, ctx.seg_len, ctx.broadcast_x, ctx.D = _owner(graph), noise, seg_len, broadcast_x, D
+        ctx.shapes = (None if p0 is None else p0.shape, None if p1 is None else p1.shape)
+        ctx.save_for_backward(x, w, out, cnt)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, w, out, cnt = ctx.saved_tensors
+        graph, noise, D = ctx.graph, ctx.noise, ctx.D
+        want_dx = ctx.needs_input_grad[0] and not ctx.broadcast_x
+        want_dw = w is not None and ctx.needs_input_grad[1]
+        want_dp = noise is not None and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
+        if not (want_dx or want_dw or want_dp):
+            return None, None, None, None, None, None, None, None
+        spec = _noise_spec(noise) if noise is not None else (_explicit_spec(w) if w is not None else _none_spec())
+        dx, dw, t0, t1 = _max_bwd_raw(graph.csr_t, x, out, cnt, _f32c(grad_out), D, spec, ctx.seg_len, want_dx, want_dw,
+                                      want_dp, ctx.broadcast_x)
+        dp = [None, None]
+        if want_dp:
+            xs = x if not ctx.broadcast_x else x.reshape(1, D).expand(t0.shape[0], D).contiguous()
+            c0, c1 = coldot(xs, t0, t1)
+            for i, (d, shape) in enumerate(((c0, ctx.shapes[0]), (c1, ctx.shapes[1]))):
+                if ctx.needs_input_grad[2 + i]:
+                    dp[i] = d.sum_to_size(shape) if d.dim() >= len(shape) and shape != d.shape else d.reshape(shape)
+        return dx, dw, dp[0], dp[1], None, None, None, None
+
+
+def _max_fused_route(graph, x, noise, w, grad):
+    """Whether aggregate_max takes stag_agg_max_fwd / _bwd (see aggregate_max)."""
+    if not FUSED_MAX or not x.is_cuda or getattr(graph, "is_shard", False):
+        return False
+    if w is not None and not w.is_cuda:
+        return False
+    if noise is None:
+        return True
+    if noise.in_norm or noise.n_samples != 1 or (noise.kind == _lib.NOISE_EXPLICIT and getattr(noise, "group", 0) > 1):
+        return False
+    live = (noise.grad_params is not None and torch.is_grad_enabled()
+            and any(torch.is_tensor(p) and p.requires_grad for p in noise.grad_params))
+    if live and noise.param_mode > _lib.PARAM_PER_CHANNEL:
+        return False
+    if grad and noise.param_mode == _lib.PARAM_PER_EDGE1:      # (stag_agg_max_bwd: STAG_ENOSYS)
+        return False
+    return True
+
+
+def aggregate_max(graph, x, weight=None, seg_len=DEFAULT_SEG_LEN, _broadcast_x=False):
     """out[v,:] = max_{e=(u->v)} w[e,:] * x[u,:], 0 for rows without in-edges (DGL's `fn.max`;
-    GraphSAGE 'pool', stag/zoo/graph_sage.py:90-93).  Not a fused path: the messages are formed
-    ([E, D]: a kernel-backed gather, the noise materialised) and reduced with scatter-amax."""
-    if x.dim() != 2:
+    GraphSAGE 'pool', stag/zoo/graph_sage.py:90-93).
+
+    On the GPU one fused pass (stag_agg_max_fwd): the noise is drawn in the kernel, no message tensor exists, and the
+    backward walks the source-major CSR (stag_agg_max_bwd).  Every maximal message of a row gets an equal share of
+    its gradient, as torch.scatter_reduce(amax) gives (except where a maximum is exactly +-0: include_self=False
+    counts the zero start there too, the fused route does not).  Node-range shards, in-norm noise, Monte-Carlo
+    batches, live per-edge parameters and CPU tensors take the composed route: the messages are formed ([E, D]: a
+    kernel-backed gather, the noise materialised) and reduced with scatter-amax.
+    _broadcast_x: x is one row [1, D] (or [D]) gathered for every edge (update_all(copy_e, max))."""
+    if x.dim() != 2 and not _broadcast_x:
         raise ValueError("aggregate_max expects x of shape [N, D]")
+    noise = weight if isinstance(weight, EdgeNoise) else None
+    w = weight if torch.is_tensor(weight) else None
+    D = x.numel() if _broadcast_x else x.shape[1]
+    if w is not None:
+        if w.shape[0] != graph.number_of_edges():
+            raise AssertionError("edge_weight.shape[0] != number_of_edges")
+        if w.dim() == 1:
+            w = w.unsqueeze(1)
+    if noise is not None and noise.dn != D:
+        raise ValueError(f"noise width {noise.dn} != feature width {D}")
+    grad_on = torch.is_grad_enabled()
+    live = (noise is not None and noise.grad_params is not None and grad_on
+            and any(torch.is_tensor(p) and p.requires_grad for p in noise.grad_params))
+    grad = grad_on and (x.requires_grad or (w is not None and w.requires_grad) or live)
+    if _max_fused_route(graph, x, noise, w, grad):
+        if w is not None and w.shape[1] != D:
+            w = w.expand(w.shape[0], D)
+        if not grad:
+            # nothing to differentiate: straight to the library (no autograd node)
+            if noise is not None:
+                spec = _noise_spec(noise)
+            elif w is not None:
+                spec = _explicit_spec(_f32c(w))
+            else:
+                spec = _none_spec()
+            return _max_fwd_raw(graph.csr, _f32c(x), D, spec, seg_len, False, _broadcast_x)[0]
+        p0 = p1 = None
+        if live:
+            p0, p1 = (torch.as_tensor(p, dtype=torch.float32, device=x.device) for p in noise.grad_params)
+        return _AggregateMax.apply(x, w, p0, p1, graph, noise, seg_len, _broadcast_x)
+    if _broadcast_x:
+        x = x.reshape(1, D).expand(graph.number_of_src_nodes() if hasattr(graph, "number_of_src_nodes")
+                                   else graph.number_of_nodes(), D).contiguous()
     m = gather_rows(graph, x, "src")
     if isinstance(weight, EdgeNoise):
         weight = weight.materialize()

@@ -99,7 +99,7 @@ class GraphSAGE(torch.nn.Module):
             neigh = ops.aggregate(graph, feat_src, edge_weight, reduce="sum")
             degs = graph.in_degrees().to(feat_dst)
             h_neigh = ops.node_linear((neigh + feat_dst) / (degs.unsqueeze(-1) + 1), self.fc_neigh.weight.t())
-        elif self._aggre_type == "pool":     # max reducer: composed, not fused (ops.aggregate_max)
+        elif self._aggre_type == "pool":     # max reducer: the fused stag_agg_max_fwd / _bwd (ops.aggregate_max)
             h_neigh = self.fc_neigh(ops.aggregate_max(graph, torch.relu(self.fc_pool(feat_src)), edge_weight))
         else:   # 'lstm' (stag/zoo/graph_sage.py:97-99): composed, not fused — no BASELINE config or script uses it
             h_neigh = self.fc_neigh(self._lstm_reduce(graph, feat_src, edge_weight))
