@@ -561,6 +561,25 @@ int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const float* el, co
                  const stag_noise_spec* spec, const float* norm_scale, const stag_gat_drop* drop,
                  float* out, float* stats_out, void* stream);
 
+/* n_samples Monte-Carlo draws of stag_gat_fwd from ONE gather of the ft rows per pass (the reference's Monte-Carlo
+ * loop, stag/models.py:45-55, on a first GAT layer: the rows are the same for every sample, only the H-wide draws
+ * differ).  Sample s is stag_gat_fwd with spec.offset + s * offset_stride (mod 2^64, plus *spec.epoch as usual), bit
+ * for bit: out + s * out_stride [M, H, F] and, when stats_out is not NULL, stats_out + s * stats_stride [M, 2H]
+ * (strides in floats; out_stride a multiple of 4).  A pass carries up to 4 samples (2 where a row takes 4 chunks of
+ * 4 channels per lane); more run as further passes inside the call.
+ * Cooperative form only: a block plan (stag_plan.block_ptr), F % 4 == 0, H <= 16, H * F <= 1024, H * lanes_per_head
+ * <= 256, 16-byte aligned ft / out; else STAG_ENOSYS, as is a launch across a 2^32 position boundary.  STAG_EINVAL:
+ * a NULL pointer, n_samples < 1, offset_stride < 0, strides smaller than one sample, kind NONE / EXPLICIT / unknown,
+ * param_mode other than SCALAR / PER_CHANNEL (per head), in_norm, deriv, pos_base outside the counter word.  No
+ * attention dropout.  Workspace (plan->workspace, with segments): stag_gat_fwd_mc_workspace_bytes(n_seg, H, F,
+ * n_samples) = stag_gat_workspace_bytes(n_seg, H, F) * min(n_samples, 4).  Every argument is checked before any
+ * device work.                                                                                                     */
+size_t stag_gat_fwd_mc_workspace_bytes(int32_t n_seg, int32_t H, int32_t F, int32_t n_samples);
+int stag_gat_fwd_mc(const stag_csr* csr, const stag_plan* plan, const float* el, const float* er,
+                    const float* ft, int32_t H, int32_t F, float neg_slope, const stag_noise_spec* spec,
+                    int32_t n_samples, int64_t offset_stride, float* out, int64_t out_stride,
+                    float* stats_out, int64_t stats_stride, void* stream);
+
 /* The attention values a[eid, h] = exp(e[p,h] - m[v,h]) / l[v,h] (get_attention=True,
  * stag/zoo/gat.py:146-147) from the statistics of stag_gat_fwd; same spec (the noisy logits are
  * redrawn from their counters).                                                               */

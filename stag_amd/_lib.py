@@ -171,6 +171,10 @@ def bind(path):
     l.stag_gat_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     l.stag_gat_fwd.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, _vp, _vp, C.c_int32, C.c_int32,
                                C.c_float, C.POINTER(NoiseSpec), _vp, C.POINTER(GatDrop), _vp, _vp, _vp]
+    l.stag_gat_fwd_mc_workspace_bytes.restype = C.c_size_t
+    l.stag_gat_fwd_mc_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    l.stag_gat_fwd_mc.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_float,
+                                  C.POINTER(NoiseSpec), C.c_int32, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp]
     l.stag_gat_attn.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, _vp, C.c_int32, C.c_float,
                                 C.POINTER(NoiseSpec), _vp, _vp, _vp, _vp]
     l.stag_gat_bwd_edge.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, _vp, _vp, _vp, _vp, _vp,

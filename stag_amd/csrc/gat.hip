@@ -747,6 +747,307 @@ __global__ __launch_bounds__(kBlkThreads) STAG_GAT_SGPR_ATTR void gat_fwd_block_
   GAT_TS(6)
 }
 
+// ---- Monte-Carlo form of the cooperative forward (stag_gat_fwd_mc) -------------------------------------------------
+// The reference's models average S noisy passes (stag/models.py:45-55, :67-68); on a first layer every pass gathers the
+// same ft rows and only the H-wide draws differ.  gat_fwd_mc_block_kernel is gat_fwd_block_kernel carrying `ns` <= SP
+// samples per launch: phase 1 draws the H weights of every sample from one load of el / er / the source id (sample s
+// at the key advanced by s * stride), phase 1b forms each sample's softmax statistics, phase 2 gathers each row ONCE
+// and folds it into SP accumulator sets.  Per sample the arithmetic, its order and the padding of a round are those of
+// gat_fwd_block_kernel<LPE, CPL, NRF> — sample s is the single-sample launch at offset + s * stride, bit for bit.
+// LDS: ns x (256 H + 64 H) floats of logits and statistics + the batch records, padded to STAG_GAT_LDS_MIN as the
+// single-sample kernel is.  Segment states: [slot][wsp][ws_stride], one ticket per segment for all its samples; the last
+// arriver merges sample by sample (the merge's registers are the single-sample kernel's, not SP times them).
+#ifndef STAG_GAT_MC_SP
+#define STAG_GAT_MC_SP 4          // samples per pass, rows of 1 or 2 chunks per lane (H * lanes_per_head <= 128)
+#endif
+#ifndef STAG_GAT_MC_SP_WIDE
+#define STAG_GAT_MC_SP_WIDE 2     // samples per pass, rows of 4 chunks per lane (PPI's 4 x 256): 16 accumulators each
+#endif
+constexpr int kGatMcMaxSP = 4;    // the workspace is sized for this many samples (stag_gat_fwd_mc_workspace_bytes)
+static_assert(STAG_GAT_MC_SP >= 1 && STAG_GAT_MC_SP <= kGatMcMaxSP && STAG_GAT_MC_SP_WIDE >= 1 &&
+              STAG_GAT_MC_SP_WIDE <= kGatMcMaxSP, "samples per pass: 1..4");
+
+struct GatMcArgs {
+  GatArgs a;               // a.key: sample 0 of this pass; a.out / a.stats: sample 0's rows
+  uint64_t stride;         // offset step between consecutive samples
+  int64_t out_stride;      // floats between two samples' out
+  int64_t stats_stride;    // floats between two samples' stats
+  int32_t ns;              // samples of this pass, 1..SP
+  int32_t wsp;             // segment states per slot of the workspace: min(n_samples, SP)
+};
+
+template <int LPE, int CPL, int NRF, int SP>
+__global__ __launch_bounds__(kBlkThreads) void gat_fwd_mc_block_kernel(const GatMcArgs g) {
+  extern __shared__ __align__(16) float lds[];
+  const GatArgs& a = g.a;
+  const int H = a.H, F = a.F, HF = a.HF, ns = g.ns;
+  const int EH = kBlkEdges * H, UH = kBlkUnits * H;   // floats per sample: logits, statistics
+  float* s_w = lds;                                   // [ns][kBlkEdges][H] logits, then p = exp(e - m)
+  float* s_m = s_w + ns * EH;                         // [ns][kBlkUnits][H]
+  float* s_l = s_m + ns * UH;                         // [ns][kBlkUnits][H]
+  int* s_u = reinterpret_cast<int*>(s_l + ns * UH);   // [kBlkEdges] source row of each edge
+  int* s_start = s_u + kBlkEdges;                     // [kBlkUnits + 1] first edge slot of each unit
+  int4* s_unit = reinterpret_cast<int4*>(s_start + kBlkUnits + 4);   // [kBlkUnits] (row, start, len, slot); 16-B aligned
+  const int t = threadIdx.x;
+  const int ub = a.block_ptr[blockIdx.x], nu = a.block_ptr[blockIdx.x + 1] - ub;
+
+  // ---- the batch: unit records, edge-slot prefix -----------------------------------------------
+  if (t < kBlkUnits) {
+    int4 q = make_int4(0, 0, 0, -1);
+    if (t < nu) q = *reinterpret_cast<const int4*>(a.units + ub + t);
+    s_unit[t] = q;
+    int incl = q.z;
+#pragma unroll
+    for (int d = 1; d < kBlkUnits; d <<= 1) {
+      const int up = __shfl_up(incl, d, kBlkUnits);
+      if (t >= d) incl += up;
+    }
+    s_start[t + 1] = incl;
+    if (t == 0) s_start[0] = 0;
+  }
+  __syncthreads();
+  const int ne = s_start[nu];
+
+  // ---- phase 1: thread t <-> edge slot t; el / er / the source id once, the draws of every sample --------------
+  if (t < ne) {
+    int lo = 0, hi = nu;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (s_start[mid] <= t) lo = mid; else hi = mid;
+    }
+    const int4 q = s_unit[lo];
+    const int row = (q.w >= 0) ? a.long_rows[q.x] : q.x;
+    const int p = q.y + (t - s_start[lo]);
+    const int u = a.indices[p];
+    s_u[t] = u;
+    const int64_t ed = a.eid ? a.eid[p] : p;
+    const uint32_t n = a.pos_lo + (a.nidx ? (uint32_t)a.nidx[p] : (uint32_t)p);
+    const PhiloxKey key = resolve_epoch(a.key);
+    const int nchunk = (H + 3) / 4;
+    const bool h4 = (H & 3) == 0 && a.hvec;
+    for (int cc = 0; cc < nchunk; ++cc) {
+      float sl4[4], sr4[4];
+      if (h4) {
+        load4(a.el + (int64_t)u * H, 4 * cc, H, true, sl4);
+        load4(a.er + (int64_t)row * H, 4 * cc, H, true, sr4);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int h = 4 * cc + j;
+          sl4[j] = h < H ? a.el[(int64_t)u * H + h] : 0.f;
+          sr4[j] = h < H ? a.er[(int64_t)row * H + h] : 0.f;
+        }
+      }
+      for (int s = 0; s < ns; ++s) {
+        float w[4];
+        head_w4(a, key_plus(key, (uint64_t)s * g.stride), n, ed, (uint32_t)cc, w);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int h = 4 * cc + j;
+          if (h < H) {
+            const float sL = sl4[j] + sr4[j];
+            const float lr = sL > 0.f ? sL : a.neg_slope * sL;
+            s_w[s * EH + t * H + h] = (w[j] * 1.0f) * lr;    // (the single-sample form with no in-norm factor)
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 1b: thread <-> (sample, unit, head): softmax statistics, logits -> p -----------------------------
+  for (int i = t; i < ns * nu * H; i += kBlkThreads) {
+    const int s = i / (nu * H), jh = i - s * (nu * H);
+    const int j = jh / H, h = jh - j * H;
+    float* w = s_w + s * EH;
+    const int e0 = s_start[j], e1 = s_start[j + 1];
+    float m = -INFINITY;
+    for (int e = e0; e < e1; ++e) m = fmaxf(m, w[e * H + h]);
+    float l = 0.f;
+    for (int e = e0; e < e1; ++e) {
+      const float pe = __expf(w[e * H + h] - m);
+      w[e * H + h] = pe;
+      l += pe;
+    }
+    s_m[s * UH + jh] = m;
+    s_l[s * UH + jh] = l;
+  }
+  __syncthreads();
+
+  // ---- phase 2: a team per unit; each row gathered once, folded into SP accumulator sets ------------------------
+  constexpr int TEAMS = kBlkThreads / LPE, NR = NRF;
+  const int team = t / LPE, c = t % LPE;
+  const int team_lane0 = (int)(t & 63) - c;
+  int k0[CPL], hl[CPL];
+  bool kin[CPL];
+#pragma unroll
+  for (int cj = 0; cj < CPL; ++cj) lane_chunk(c + LPE * cj, H, F, a.lphp, k0[cj], kin[cj], hl[cj]);
+  const __amdgpu_buffer_rsrc_t rft =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.ft), 0, (int)a.ft_bytes, 0x00020000);
+  const bool ft_buf = a.ft_bytes != 0;
+  for (int j = team; j < nu; j += TEAMS) {
+    const int4 q = s_unit[j];
+    const int e0 = s_start[j], e1 = s_start[j + 1];
+    float acc[SP][CPL][4];
+#pragma unroll
+    for (int s = 0; s < SP; ++s)
+#pragma unroll
+      for (int cj = 0; cj < CPL; ++cj) acc[s][cj][0] = acc[s][cj][1] = acc[s][cj][2] = acc[s][cj][3] = 0.f;
+    // (the round of gat_fwd_block_kernel's branch-free form: NR loads issued back to back, positions past the unit's
+    //  end clamped to its last edge with weight 0; samples past ns carry weight 0 and are never stored)
+    for (int e = e0; e < e1; e += NR) {
+      float fv[NR][CPL][4], pe[NR][SP][CPL];
+      int u[NR];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const int er = min(e + r, e1 - 1);
+        u[r] = s_u[er];
+#pragma unroll
+        for (int s = 0; s < SP; ++s) {
+#pragma unroll
+          for (int cj = 0; cj < CPL; ++cj) {
+            const float wv = (s < ns) ? s_w[s * EH + er * H + (kin[cj] ? hl[cj] : 0)] : 0.f;
+            pe[r][s][cj] = (e + r < e1) ? wv : 0.f;
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+#pragma unroll
+        for (int cj = 0; cj < CPL; ++cj) {
+          if (ft_buf) bufrow4(rft, u[r], (uint32_t)HF * 4u, (uint32_t)k0[cj] * 4u, fv[r][cj]);
+          else loadrow4(a.ft + (int64_t)u[r] * HF + k0[cj], k0[cj], HF, true, fv[r][cj]);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+#pragma unroll
+        for (int s = 0; s < SP; ++s) {
+#pragma unroll
+          for (int cj = 0; cj < CPL; ++cj) {
+#pragma unroll
+            for (int x = 0; x < 4; ++x) acc[s][cj][x] = __builtin_fmaf(pe[r][s][cj], fv[r][cj][x], acc[s][cj][x]);
+          }
+        }
+      }
+    }
+    if (q.w < 0) {
+      // ---- whole row: normalise and store every sample ---------------------------------------------------------
+#pragma unroll
+      for (int s = 0; s < SP; ++s) {
+        if (s >= ns) break;
+        float* out_s = a.out + (int64_t)s * g.out_stride;
+#pragma unroll
+        for (int cj = 0; cj < CPL; ++cj) {
+          if (!kin[cj]) continue;
+          const float m = s_m[s * UH + j * H + hl[cj]], l = s_l[s * UH + j * H + hl[cj]];
+          const float inv = (l > 0.f) ? 1.0f / l : 0.f;
+          float o[4];
+#pragma unroll
+          for (int x = 0; x < 4; ++x) o[x] = acc[s][cj][x] * inv;
+          store4_out(out_s + (int64_t)q.x * HF, k0[cj], HF, true, o);
+          if (a.stats && k0[cj] % F == 0) {
+            float* st = a.stats + (int64_t)s * g.stats_stride;
+            st[(int64_t)q.x * 2 * H + hl[cj]] = m;
+            st[(int64_t)q.x * 2 * H + H + hl[cj]] = l;
+          }
+        }
+      }
+      continue;
+    }
+    // ---- segment: publish (acc, m, l) of every sample write-through, take ONE ticket; the last arriver merges ------
+    const int v = q.x, slot = q.w, row = a.long_rows[v];
+    const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(a.ws, 0, (int)a.ws_bytes, 0x00020000);
+#pragma unroll
+    for (int s = 0; s < SP; ++s) {
+      if (s >= ns) break;
+      const uint32_t base = ((uint32_t)slot * (uint32_t)g.wsp + (uint32_t)s) * ((uint32_t)a.ws_stride * 4u);
+#pragma unroll
+      for (int cj = 0; cj < CPL; ++cj) {
+        if (!kin[cj]) continue;
+        store4_sc1(rws, base + (uint32_t)k0[cj] * 4u, k0[cj], HF, true, acc[s][cj]);
+        if (k0[cj] % F == 0) {
+          const float m = s_m[s * UH + j * H + hl[cj]], l = s_l[s * UH + j * H + hl[cj]];
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(m), rws, (int)(base + (uint32_t)(HF + hl[cj]) * 4u), 0, 16);
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(l), rws, (int)(base + (uint32_t)(HF + H + hl[cj]) * 4u), 0, 16);
+        }
+      }
+    }
+    const int s0 = a.long_seg_ptr[v], s1 = a.long_seg_ptr[v + 1];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    int ticket = 0;
+    if (c == 0)
+      ticket = __hip_atomic_fetch_add(a.seg_counters + v, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ticket = __builtin_amdgcn_ds_bpermute(team_lane0 << 2, ticket);
+    if (ticket != (s1 - s0) - 1) continue;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (c == 0) a.seg_counters[v] = 0;
+    // the merge of gat_fwd_block_kernel, one sample at a time: segment sg of sample s is state sg * wsp + s
+#pragma unroll 1
+    for (int s = 0; s < ns; ++s) {
+      const float* ws = a.ws + (int64_t)s * a.ws_stride;
+      const int64_t wst = (int64_t)g.wsp * a.ws_stride;
+      float* out_s = a.out + (int64_t)s * g.out_stride;
+#pragma unroll
+      for (int cj = 0; cj < CPL; ++cj) {
+        if (!kin[cj]) continue;
+        float M = -INFINITY, L = 0.f;
+        float A[4] = {0.f, 0.f, 0.f, 0.f};
+        constexpr int NFM = CPL == 1 ? kGatMergeNF : 1;
+        const int lph = a.lphp;
+        if (CPL == 1 && lph >= 2 && lph * 4 == F && H * lph == LPE) {
+          const int gq = c & (lph - 1);
+          for (int sg = s0 + gq; sg < s1; sg += 2 * NFM * lph) {
+            float mm[2 * NFM];
+#pragma unroll
+            for (int i = 0; i < 2 * NFM; ++i) mm[i] = ws[(int64_t)min(sg + i * lph, s1 - 1) * wst + HF + hl[cj]];
+#pragma unroll
+            for (int i = 0; i < 2 * NFM; ++i) M = fmaxf(M, mm[i]);
+          }
+          for (int d = 1; d < lph; d <<= 1) M = fmaxf(M, __shfl_xor(M, d));
+        } else {
+          for (int sg = s0; sg < s1; sg += 2 * NFM) {
+            float mm[2 * NFM];
+#pragma unroll
+            for (int i = 0; i < 2 * NFM; ++i) mm[i] = ws[(int64_t)min(sg + i, s1 - 1) * wst + HF + hl[cj]];
+#pragma unroll
+            for (int i = 0; i < 2 * NFM; ++i) M = fmaxf(M, mm[i]);
+          }
+        }
+        for (int sg = s0; sg < s1; sg += NFM) {
+          float tt[NFM][4], ms[NFM], ls[NFM];
+#pragma unroll
+          for (int i = 0; i < NFM; ++i) {
+            const float* wr = ws + (int64_t)min(sg + i, s1 - 1) * wst;
+            load4(wr, k0[cj], HF, true, tt[i]);
+            ms[i] = wr[HF + hl[cj]];
+            ls[i] = wr[HF + H + hl[cj]];
+          }
+#pragma unroll
+          for (int i = 0; i < NFM; ++i) {
+            if (sg + i < s1) {
+              const float sc = __expf(ms[i] - M);
+              L += ls[i] * sc;
+#pragma unroll
+              for (int x = 0; x < 4; ++x) A[x] = __builtin_fmaf(tt[i][x], sc, A[x]);
+            }
+          }
+        }
+        const float inv = (L > 0.f) ? 1.0f / L : 0.f;
+#pragma unroll
+        for (int x = 0; x < 4; ++x) A[x] *= inv;
+        store4_out(out_s + (int64_t)row * HF, k0[cj], HF, true, A);
+        if (a.stats && k0[cj] % F == 0) {
+          float* st = a.stats + (int64_t)s * g.stats_stride;
+          st[(int64_t)row * 2 * H + hl[cj]] = M;
+          st[(int64_t)row * 2 * H + H + hl[cj]] = L;
+        }
+      }
+    }
+  }
+}
+
 // Attention values a[eid, h] = exp(logit - m[v,h]) / l[v,h] (get_attention=True,
 // stag/zoo/gat.py:146-147) from the row statistics of gat_fwd_kernel: 8 lanes per unit of the
 // plan, a lane per edge; the noisy logit is redrawn from its counters.
@@ -1774,6 +2075,114 @@ extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const fl
   }
 #undef STAG_GAT_LAUNCH
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
+}
+
+extern "C" size_t stag_gat_fwd_mc_workspace_bytes(int32_t n_seg, int32_t H, int32_t F, int32_t n_samples) {
+  if (n_samples <= 0) return 0;
+  return stag_gat_workspace_bytes(n_seg, H, F) * (size_t)(n_samples < kGatMcMaxSP ? n_samples : kGatMcMaxSP);
+}
+
+// n_samples draws of stag_gat_fwd from one gather of the ft rows per pass of SP samples (gat_fwd_mc_block_kernel).
+// Every argument is checked before anything is launched.
+extern "C" int stag_gat_fwd_mc(const stag_csr* csr, const stag_plan* plan, const float* el, const float* er,
+                               const float* ft, int32_t H, int32_t F, float neg_slope, const stag_noise_spec* spec,
+                               int32_t n_samples, int64_t offset_stride, float* out, int64_t out_stride,
+                               float* stats_out, int64_t stats_stride, void* stream) {
+  if (!csr || !csr->indptr || csr->n_dst < 0 || csr->n_edges < 0 || csr->n_src < 0) return STAG_EINVAL;
+  if (!spec || !out || !el || !er || !ft || (csr->n_edges > 0 && !csr->indices)) return STAG_EINVAL;
+  if (H <= 0 || F <= 0 || n_samples < 1 || offset_stride < 0) return STAG_EINVAL;
+  const int64_t HF64 = (int64_t)H * F;
+  if (n_samples > 1 && (out_stride < (int64_t)csr->n_dst * HF64 || (stats_out && stats_stride < (int64_t)csr->n_dst * 2 * H)))
+    return STAG_EINVAL;
+  if (spec->kind != STAG_NOISE_NORMAL && spec->kind != STAG_NOISE_UNIFORM && spec->kind != STAG_NOISE_BERNOULLI)
+    return STAG_EINVAL;
+  if (spec->param_mode != STAG_PARAM_SCALAR && spec->param_mode != STAG_PARAM_PER_CHANNEL) return STAG_EINVAL;
+  if (spec->param_mode == STAG_PARAM_PER_CHANNEL && (!spec->p0 || (spec->kind != STAG_NOISE_BERNOULLI && !spec->p1)))
+    return STAG_EINVAL;
+  if (spec->in_norm || spec->deriv) return STAG_EINVAL;
+  const int prc = check_positions(spec, csr->n_edges, H, true);
+  if (prc) return prc;
+  if (spec->chunk_base != 0) return STAG_ENOSYS;   // heads are not channel-sharded
+  // the cooperative form only: a block plan, F % 4 == 0, H <= 16, H * F <= 1024, a row within 256 lanes, 16-B rows
+  const int lphp = (F % 4 == 0) ? lanes_per_head(F) : 0;
+  if (!plan || plan->n_units <= 0 || !plan->units || !plan->block_ptr || plan->n_blocks <= 0) return STAG_ENOSYS;
+  if (lphp == 0 || H > kBlkMaxH || HF64 > 1024 || lphp > 64 || H * lphp > 256 || plan->seg_len > kBlkEdges) return STAG_ENOSYS;
+  if (!aligned16(plan->units) || !aligned16(ft) || !aligned16(out) || (n_samples > 1 && out_stride % 4 != 0))
+    return STAG_ENOSYS;
+  const int HF = (int)HF64;
+  const int nchunk = H * lphp;
+  int lpe = 4;
+  while (lpe < nchunk && lpe < 64) lpe <<= 1;
+  const int cpl = nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4);
+  const int sp = cpl == 4 ? STAG_GAT_MC_SP_WIDE : STAG_GAT_MC_SP;
+  const int wsp = n_samples < sp ? n_samples : sp;
+
+  GatMcArgs g{};
+  GatArgs& a = g.a;
+  a.indptr = csr->indptr; a.indices = csr->indices; a.eid = csr->eid; a.nidx = csr->nidx;
+  a.n_rows = csr->n_dst; a.el = el; a.er = er; a.ft = ft;
+  a.H = H; a.F = F; a.HF = HF;
+  a.neg_slope = neg_slope; a.kind = spec->kind; a.p0 = spec->p0; a.p1 = spec->p1;
+  const bool logs = spec->kind == STAG_NOISE_NORMAL && spec->p1_log;
+  a.p0s = spec->p0_scalar; a.p1s = logs ? expf(spec->p1_scalar) : spec->p1_scalar;
+  a.pmode = spec->param_mode;
+  a.relu = (spec->relu ? kFlagRelu : 0) | (logs ? kFlagLogScale : 0);
+  a.key.k0 = (uint32_t)(spec->seed & 0xFFFFFFFFull); a.key.k1 = (uint32_t)(spec->seed >> 32);
+  a.key.epoch = spec->epoch;
+  a.pos_lo = (uint32_t)((uint64_t)spec->pos_base & 0xFFFFFFFFull);
+  a.pos_hi = (uint32_t)((uint64_t)spec->pos_base >> 32);
+  const uint64_t ftb = (uint64_t)csr->n_src * (uint64_t)HF * 4u;
+  a.ft_bytes = (ftb < (1ull << 32) && csr->n_src < (1 << 24)) ? (uint32_t)ftb : 0u;
+  a.units = plan->units; a.n_units = plan->n_units;
+  a.ws_stride = (HF + 2 * H + 3) & ~3;
+  if (plan->n_seg > 0) {
+    if (!plan->long_rows || !plan->long_seg_ptr || !plan->workspace || !plan->seg_counters) return STAG_EINVAL;
+    const size_t need = stag_gat_workspace_bytes(plan->n_seg, H, F) * (size_t)wsp;
+    if (plan->workspace_bytes < need) return STAG_ENOMEM;
+    if (need >= (1ull << 32)) return STAG_ENOSYS;     // segment states go through a 32-bit buffer descriptor
+    if (!aligned16(plan->workspace)) return STAG_ENOSYS;
+    a.long_rows = plan->long_rows; a.long_seg_ptr = plan->long_seg_ptr; a.n_long = plan->n_long;
+    a.seg_counters = plan->seg_counters; a.ws = plan->workspace;
+    a.ws_bytes = (uint32_t)need; a.n_seg = plan->n_seg;
+  }
+  if (csr->n_dst == 0) return STAG_OK;
+  a.block_ptr = plan->block_ptr;
+  a.lphp = lphp;
+  a.hvec = aligned16(el) && aligned16(er);
+  g.stride = (uint64_t)offset_stride;
+  g.out_stride = out_stride; g.stats_stride = stats_stride;
+  g.wsp = wsp;
+  const dim3 gb(plan->n_blocks);
+  const bool local = plan->xcd_order != nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  for (int32_t s0 = 0; s0 < n_samples; s0 += sp) {
+    g.ns = (n_samples - s0 < sp) ? n_samples - s0 : sp;
+    const uint64_t off = spec->offset + (uint64_t)s0 * (uint64_t)offset_stride;
+    a.key.o0 = (uint32_t)(off & 0xFFFFFFFFull); a.key.o1 = (uint32_t)(off >> 32);
+    a.out = out + (int64_t)s0 * out_stride;
+    a.stats = stats_out ? stats_out + (int64_t)s0 * stats_stride : nullptr;
+    size_t lds = (size_t)g.ns * (kBlkEdges * H + 2 * kBlkUnits * H) * sizeof(float) +
+                 (size_t)(kBlkEdges + kBlkUnits + 4) * sizeof(int) + (size_t)kBlkUnits * sizeof(int4);
+    if (lds < STAG_GAT_LDS_MIN) lds = STAG_GAT_LDS_MIN;
+    // the (LPE, CPL, NRF) stag_gat_fwd launches for the shape: the same rounds, so the same bits per sample
+#define STAG_MC_LAUNCH(L, Cc, N, P) hipLaunchKernelGGL((gat_fwd_mc_block_kernel<L, Cc, N, P>), gb, dim3(kBlkThreads), lds, s, g)
+    if (cpl == 4) {
+      if (local) STAG_MC_LAUNCH(64, 4, STAG_GAT_NR_FWD_LOCAL, STAG_GAT_MC_SP_WIDE);
+      else STAG_MC_LAUNCH(64, 4, STAG_GAT_NR_FWD, STAG_GAT_MC_SP_WIDE);
+    } else if (cpl == 2) {
+      if (local) STAG_MC_LAUNCH(64, 2, STAG_GAT_NR_FWD_LOCAL, STAG_GAT_MC_SP);
+      else STAG_MC_LAUNCH(64, 2, STAG_GAT_NR_FWD, STAG_GAT_MC_SP);
+    } else switch (lpe) {
+      case 64: STAG_MC_LAUNCH(64, 1, STAG_GAT_NR_FWD_NARROW, STAG_GAT_MC_SP); break;
+      case 32: STAG_MC_LAUNCH(32, 1, STAG_GAT_NR_FWD_NARROW, STAG_GAT_MC_SP); break;
+      case 16: STAG_MC_LAUNCH(16, 1, STAG_GAT_NR_FWD_NARROW, STAG_GAT_MC_SP); break;
+      case 8: STAG_MC_LAUNCH(8, 1, STAG_GAT_NR_FWD_NARROW, STAG_GAT_MC_SP); break;
+      default: STAG_MC_LAUNCH(4, 1, STAG_GAT_NR_FWD_NARROW, STAG_GAT_MC_SP); break;
+    }
+#undef STAG_MC_LAUNCH
+    if (hipGetLastError() != hipSuccess) return STAG_EIO;
+  }
+  return STAG_OK;
 }
 
 // the argument block the attention / backward kernels share with the forward

@@ -1,5 +1,5 @@
 // torch_ext.cpp — PyTorch-ROCm front end of the hot calls: TORCH_LIBRARY ops `stag::agg_fwd`, `stag::agg_bwd` and (round 4)
-// `stag::agg_fwd_mc`, `stag::agg_bwd_dp`, `stag::gat_fwd`, `stag::gat_bwd`, `stag::agg_max_fwd`, `stag::agg_max_bwd` over the C ABI of include/stag_hip.h (the boundary stays that header; this file only
+// `stag::agg_fwd_mc`, `stag::agg_bwd_dp`, `stag::gat_fwd`, `stag::gat_fwd_mc`, `stag::gat_bwd`, `stag::agg_max_fwd`, `stag::agg_max_bwd` over the C ABI of include/stag_hip.h (the boundary stays that header; this file only
 // marshals tensors into its structs, allocates outputs with the caching allocator and picks the current
 // HIP stream).  Replaces the ctypes marshalling on the per-layer path (stag_amd/ops.py falls back to ctypes
 // when this module is not built); the ops are visible to the dispatcher and carry Meta kernels, so a
@@ -359,6 +359,43 @@ std::tuple<Tensor, Tensor> gat_fwd_meta(const Tensor& indptr, const Tensor&, Opt
   return {at::empty({n, H, F}, ft.options()), want_stats ? at::empty({n, 2 * H}, ft.options()) : at::empty({0}, ft.options())};
 }
 
+// [S, M, H, F] and the statistics [S, M, 2H] of S Monte-Carlo draws of gat_fwd from one gather of the ft rows per pass
+// (stag_gat_fwd_mc): sample s is gat_fwd at offset + s * offset_stride
+std::tuple<Tensor, Tensor> gat_fwd_mc(const Tensor& indptr, const Tensor& indices, OptT eid, OptT nidx, int64_t n_src, OptT units,
+                                      OptT long_rows, OptT long_seg_ptr, OptT block_ptr, OptT xcd, OptT counters,
+                                      at::IntArrayRef plan_ints, const Tensor& el, const Tensor& er, const Tensor& ft,
+                                      double neg_slope, at::IntArrayRef noise_ints, at::IntArrayRef noise_u64,
+                                      at::ArrayRef<double> noise_floats, OptT p0, OptT p1, OptT epoch, int64_t n_samples,
+                                      int64_t offset_stride, bool want_stats) {
+  TORCH_CHECK(ft.is_cuda() && ft.scalar_type() == at::kFloat && ft.is_contiguous() && ft.dim() == 3, "ft: [N, H, F] fp32");
+  TORCH_CHECK(el.is_contiguous() && er.is_contiguous() && el.scalar_type() == at::kFloat && er.scalar_type() == at::kFloat, "el, er: fp32, contiguous");
+  TORCH_CHECK(n_samples >= 1, "n_samples >= 1");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(ft.device());
+  Graph g = make_graph(indptr, indices, eid, nidx, n_src, units, long_rows, long_seg_ptr, block_ptr, xcd, counters, plan_ints);
+  const stag_noise_spec spec = make_spec(noise_ints, noise_u64, noise_floats, p0, p1, epoch);
+  const int64_t H = ft.size(1), F = ft.size(2), n = g.csr.n_dst;
+  Tensor out = at::empty({n_samples, n, H, F}, ft.options());
+  Tensor stats = want_stats ? at::empty({n_samples, n, 2 * H}, ft.options()) : at::empty({0}, ft.options());
+  Tensor ws;
+  give_workspace(g, g.has_plan ? stag_gat_fwd_mc_workspace_bytes(g.plan.n_seg, (int32_t)H, (int32_t)F, (int32_t)n_samples) : 0,
+                 ft, ws);
+  check_rc(stag_gat_fwd_mc(&g.csr, g.has_plan ? &g.plan : nullptr, el.data_ptr<float>(), er.data_ptr<float>(),
+                           ft.data_ptr<float>(), (int32_t)H, (int32_t)F, (float)neg_slope, &spec, (int32_t)n_samples,
+                           offset_stride, out.data_ptr<float>(), n * H * F, want_stats ? stats.data_ptr<float>() : nullptr,
+                           n * 2 * H, stream_of(ft)),
+           "stag_gat_fwd_mc");
+  return {out, stats};
+}
+
+std::tuple<Tensor, Tensor> gat_fwd_mc_meta(const Tensor& indptr, const Tensor&, OptT, OptT, int64_t, OptT, OptT, OptT, OptT, OptT,
+                                           OptT, at::IntArrayRef, const Tensor&, const Tensor&, const Tensor& ft, double,
+                                           at::IntArrayRef, at::IntArrayRef, at::ArrayRef<double>, OptT, OptT, OptT,
+                                           int64_t n_samples, int64_t, bool want_stats) {
+  const int64_t n = indptr.numel() - 1, H = ft.size(1), F = ft.size(2);
+  return {at::empty({n_samples, n, H, F}, ft.options()),
+          want_stats ? at::empty({n_samples, n, 2 * H}, ft.options()) : at::empty({0}, ft.options())};
+}
+
 // the whole backward with ONE gather of the [H*F] rows (stag_gat_bwd): d el [n_src, H], d er [n_dst, H], d ft [n_src, H, F]
 // and (want_dw) dw [E, H] by edge id.  The second graph / plan is the source-major orientation (its block plan required).
 std::tuple<Tensor, Tensor, Tensor, Tensor> gat_bwd(
@@ -438,6 +475,8 @@ TORCH_LIBRARY(stag, m) {
         "bool want_dx, bool want_dw, bool want_dp) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("gat_fwd(" STAG_GRAPH_ARGS "Tensor el, Tensor er, Tensor ft, float neg_slope, " STAG_NOISE_ARGS
         "Tensor? norm_scale, float[] drop_floats, int[] drop_u64, Tensor? drop_epoch, bool want_stats) -> (Tensor, Tensor)");
+  m.def("gat_fwd_mc(" STAG_GRAPH_ARGS "Tensor el, Tensor er, Tensor ft, float neg_slope, " STAG_NOISE_ARGS
+        "int n_samples, int offset_stride, bool want_stats) -> (Tensor, Tensor)");
   m.def("gat_bwd(" STAG_GRAPH_ARGS "Tensor indptr_t, Tensor indices_t, Tensor? eid_t, Tensor? nidx_t, Tensor? units_t, "
         "Tensor? long_rows_t, Tensor? long_seg_ptr_t, Tensor? block_ptr_t, Tensor? counters_t, int[] plan_ints_t, "
         "Tensor el, Tensor er, Tensor ft, Tensor stats, Tensor grad, Tensor out, float neg_slope, " STAG_NOISE_ARGS
@@ -453,6 +492,7 @@ TORCH_LIBRARY_IMPL(stag, CUDA, m) {      // the HIP backend answers to the CUDA 
   m.impl("agg_max_fwd", &agg_max_fwd);
   m.impl("agg_max_bwd", &agg_max_bwd);
   m.impl("gat_fwd", &gat_fwd);
+  m.impl("gat_fwd_mc", &gat_fwd_mc);
   m.impl("gat_bwd", &gat_bwd);
 }
 
@@ -464,5 +504,6 @@ TORCH_LIBRARY_IMPL(stag, Meta, m) {
   m.impl("agg_max_fwd", &agg_max_fwd_meta);
   m.impl("agg_max_bwd", &agg_max_bwd_meta);
   m.impl("gat_fwd", &gat_fwd_meta);
+  m.impl("gat_fwd_mc", &gat_fwd_mc_meta);
   m.impl("gat_bwd", &gat_bwd_meta);
 }

@@ -1728,7 +1728,16 @@ def gat_aggregate(graph, el, er, ft, neg_slope=0.2, weight=None, want_attn=False
     attn_drop: (p, seed, offset[, epoch]) — attention dropout (stag/zoo/gat.py:122) inside the kernels, its mask
     from its own Philox stream (attn_drop_fusable() says whether the shape has that form); attn_fn: any function of
     a[E, H] between the softmax and the sum, on the composed path.
-    On a node-range shard the inputs are this rank's rows and the call includes the exchange."""
+    On a node-range shard the inputs are this rank's rows and the call includes the exchange.
+    An EdgeNoise with n_samples > 1 (StagLayer.forward_mc) yields [n_samples, N, H, F]: gat_aggregate_mc."""
+    if isinstance(weight, EdgeNoise) and weight.n_samples > 1:
+        if want_attn or attn_fn is not None or attn_drop is not None:
+            raise NotImplementedError("Monte-Carlo samples (n_samples > 1) without attention values or dropout only")
+        import copy
+        one = copy.copy(weight)
+        one.n_samples = 1
+        return gat_aggregate_mc(graph, el, er, ft, neg_slope, one, weight.n_samples, weight.offset_stride,
+                                seg_len=seg_len, _gathered=_gathered)
     if getattr(graph, "is_shard", False) and not _gathered:
         if attn_fn is not None:
             raise NotImplementedError("a function of a[E, H] (attn_fn) is not partitioned: pass attn_drop")
@@ -1774,6 +1783,109 @@ def gat_aggregate(graph, el, er, ft, neg_slope=0.2, weight=None, want_attn=False
     if live is not None:
         return _GatAggregate.apply(el, er, ft, None, graph, noise, neg_slope, want_attn, seg_len, attn_drop, *live)
     return _GatAggregate.apply(el, er, ft, w, graph, noise, neg_slope, want_attn, seg_len, attn_drop)
+
+
+def gat_aggregate_mc(graph, el, er, ft, neg_slope, noise, n_samples, offset_stride=1, seg_len=DEFAULT_SEG_LEN,
+                     _gathered=False):
+    """[n_samples, N, H, F]: sample s == gat_aggregate(graph, el, er, ft, neg_slope, noise at offset + s *
+    offset_stride), bit for bit.  The reference's Monte-Carlo loops (stag/models.py:45-55, :67-68) on a first GAT
+    layer: el, er and ft are the same for every sample, so the fused form (stag_gat_fwd_mc) gathers each ft row once
+    per pass of up to 4 samples and only the H-wide draws, the softmax and the weighted sums repeat.  Under autograd
+    (el / er / ft carry a gradient) the forward is still batched and the backward is the loop's per-sample one-gather
+    backward (_GatAggregateMC).  Shards, in-norm, explicit / per-edge parameters, live `vi=True` parameters under
+    autograd, shapes outside the cooperative kernels, CPU tensors and n_samples == 1 take the stack of n_samples
+    ordinary gat_aggregate calls."""
+    import copy
+
+    def one(s):
+        nz = copy.copy(noise)
+        nz.offset = (noise.offset + s * offset_stride) & _MASK64
+        nz.n_samples = 1
+        return gat_aggregate(graph, el, er, ft, neg_slope, nz, seg_len=seg_len, _gathered=_gathered)
+
+    if not isinstance(noise, EdgeNoise):
+        raise TypeError("gat_aggregate_mc draws its samples from an EdgeNoise")
+    H, F = ft.shape[1], ft.shape[2]
+    live = (noise.grad_params is not None and torch.is_grad_enabled()
+            and any(torch.is_tensor(p) and p.requires_grad for p in noise.grad_params))
+    fused = (n_samples > 1 and not (getattr(graph, "is_shard", False) and not _gathered) and ft.is_cuda
+             and noise.kind >= _lib.NOISE_NORMAL and noise.param_mode <= _lib.PARAM_PER_CHANNEL and not noise.in_norm
+             and not live and int(getattr(noise, "chunk_base", 0) or 0) == 0 and gat_cooperative_shape(H, F, seg_len)
+             and graph.csr.n_dst > 0)
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (el, er, ft))
+    if fused and needs_grad:
+        fused = _GAT_BWD_FUSED and _GAT_BWD_ONE_GATHER     # the backward is the one-gather kernels' (per sample)
+    if not fused:
+        if n_samples == 1:
+            return one(0).unsqueeze(0)
+        return torch.stack([one(s) for s in range(n_samples)], 0)
+    if needs_grad:
+        return _GatAggregateMC.apply(el, er, ft, graph, noise, int(n_samples), int(offset_stride), float(neg_slope),
+                                     seg_len)
+    out, _ = _gat_fwd_mc_raw(graph.csr, _f32c(el), _f32c(er), _f32c(ft), noise, int(n_samples), int(offset_stride),
+                             float(neg_slope), seg_len, want_stats=False)
+    return out
+
+
+def _gat_fwd_mc_raw(csrv, el, er, ft, noise, n_samples, offset_stride, neg_slope, seg_len, want_stats):
+    """One stag_gat_fwd_mc call: (out [S, n_dst, H, F], stats [S, n_dst, 2H] or None)."""
+    H, F = ft.shape[1], ft.shape[2]
+    dev = _lib.require_device(el, er, ft, csrv.indptr)
+    plan_t = csrv.plan(seg_len, need=True)       # the cooperative kernels want the plan's unit batches
+    if _torch_ext.available():      # the dispatcher op (csrc/torch_ext.cpp: stag::gat_fwd_mc), same library call
+        out, stats = torch.ops.stag.gat_fwd_mc(*csrv.torch_args(), *_gat_plan_args(csrv, plan_t, dev, H * F), el, er, ft,
+                                               float(neg_slope), *noise.torch_args(), int(n_samples), int(offset_stride),
+                                               bool(want_stats))
+        return out, (stats if want_stats else None)
+    out = torch.empty((n_samples, csrv.n_dst, H, F), dtype=torch.float32, device=dev)
+    stats = torch.empty((n_samples, csrv.n_dst, 2 * H), dtype=torch.float32, device=dev) if want_stats else None
+    nbytes = _lib.lib().stag_gat_fwd_mc_workspace_bytes(plan_t["n_seg"], H, F, n_samples)
+    plan_c, _keep = _plan_struct(csrv, seg_len, 1, nbytes, dev, plan_t=plan_t, gat_width=H * F)
+    cs, spec = csrv.struct(), noise.spec()
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_gat_fwd_mc(C.byref(cs), C.byref(plan_c), _lib.ptr(el), _lib.ptr(er), _lib.ptr(ft), H, F,
+                                        float(neg_slope), C.byref(spec), n_samples, offset_stride, _lib.ptr(out),
+                                        csrv.n_dst * H * F, _lib.ptr(stats), csrv.n_dst * 2 * H, _lib.stream_of(dev))
+    _lib.check(rc, "stag_gat_fwd_mc")
+    return out, stats
+
+
+class _GatAggregateMC(torch.autograd.Function):
+    """S Monte-Carlo samples of one GAT aggregation with gradients w.r.t. el, er and ft (a first GAT layer without
+    dropout trained with n_samples_training > 1, stag/models.py:67-68): the forward is the batched stag_gat_fwd_mc
+    (one gather of the ft rows per pass), the backward the loop's per-sample one-gather backward (stag_gat_bwd with
+    sample s's statistics, output and offset), d el / d er / d ft summed over the samples."""
+
+    @staticmethod
+    def forward(ctx, el, er, ft, graph, noise, n_samples, stride, neg_slope, seg_len):
+        el, er, ft = _f32c(el), _f32c(er), _f32c(ft)
+        out, stats = _gat_fwd_mc_raw(graph.csr, el, er, ft, noise, n_samples, stride, neg_slope, seg_len, want_stats=True)
+        ctx.graph, ctx.noise, ctx.S, ctx.stride, ctx.neg_slope, ctx.seg_len = (_owner(graph), noise, n_samples, stride,
+                                                                                neg_slope, seg_len)
+        ctx.save_for_backward(el, er, ft, out, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        import copy
+        el, er, ft, out, stats = ctx.saved_tensors
+        graph = ctx.graph
+        H, F = ft.shape[1], ft.shape[2]
+        G = _f32c(grad_out)
+        d_el = d_er = d_ft = None
+        for s in range(ctx.S):
+            nz = copy.copy(ctx.noise)
+            nz.offset = (ctx.noise.offset + s * ctx.stride) & _MASK64
+            nz.n_samples = 1
+            r = _gat_bwd_fused(graph.csr, graph.csr_t, el, er, ft, stats[s], G[s], out[s], H, F, ctx.neg_slope,
+                               nz.spec(), None, False, ctx.seg_len, ft.device, spec_tensors=(nz.p0, nz.p1, nz.epoch))
+            if r is None:
+                raise NotImplementedError("the batched GAT samples need the one-gather backward (stag_gat_bwd)")
+            d_el = r[0] if d_el is None else d_el + r[0]
+            d_er = r[1] if d_er is None else d_er + r[1]
+            d_ft = r[2] if d_ft is None else d_ft + r[2]
+        return (d_el if ctx.needs_input_grad[0] else None, d_er if ctx.needs_input_grad[1] else None,
+                d_ft if ctx.needs_input_grad[2] else None, None, None, None, None, None, None)
 
 
 def _gat_composed(graph, el, er, ft, neg_slope, noise, w, want_attn, seg_len, attn_fn=None):

@@ -11,6 +11,13 @@ class GAT(torch.nn.Module):
     supports_edge_noise = True
     supports_edge_noise_grad = True   # vi=True: ops.gat_aggregate forms the [E, H] weights from the descriptor
 
+    @property
+    def supports_edge_noise_mc(self):
+        """An EdgeNoise with n_samples > 1 yields [S, N, out] (the Monte-Carlo loop batched on this layer:
+        ops.gat_aggregate_mc) — unless the layer trains with dropout: the sequential loop would draw a fresh
+        feature-dropout mask and a fresh attention-dropout mask (fused or composed) per sample."""
+        return not (self.training and (self.feat_drop.p > 0.0 or self.attn_drop.p > 0.0))
+
     def __init__(self, in_feats, out_feats, num_heads=4, feat_drop=0.0, attn_drop=0.0,
                  negative_slope=0.2, residual=False, activation=None, allow_zero_in_degree=False,
                  bias=True, last=False):
@@ -63,6 +70,10 @@ class GAT(torch.nn.Module):
 
     def forward(self, graph, feat, get_attention=False, edge_weight=None):
         H, F = self._num_heads, self._out_feats
+        n_mc = edge_weight.n_samples if isinstance(edge_weight, ops.EdgeNoise) else 1
+        if n_mc > 1 and (get_attention or not self.supports_edge_noise_mc):
+            raise NotImplementedError("Monte-Carlo samples (n_samples > 1) on a GAT layer: no attention values, and no "
+                                      "dropout in training (the loop draws its masks per sample)")
         h = self.feat_drop(feat)
         # Head widths that are not a multiple of 4 — class counts like 7, 121 on the last layer of the reference's
         # GAT scripts — run with each head zero-padded to the next multiple of 4: the padding is rows of zeros in
@@ -114,6 +125,8 @@ class GAT(torch.nn.Module):
         res = ops.gat_aggregate(graph, el, er, ft, self._negative_slope, edge_weight,
                                 want_attn=get_attention, attn_fn=drop, attn_drop=fused_drop)
         rst, attn = res if get_attention else (res, None)
+        # (n_mc > 1: rst is [S, N, H, F], the S samples of ops.gat_aggregate_mc; fc, head_dot and the residual
+        #  projection ran once, the epilogue below is elementwise per sample)
         if F_out != F:
             rst, F = rst[..., :F_out], F_out
         if self.res_fc is not None:
@@ -121,8 +134,11 @@ class GAT(torch.nn.Module):
         if self.bias is not None:
             # (the bias gradient of an odd total width goes through ops.column_sum: torch's own column reduction
             # takes a slow path when the width is not a multiple of 4)
-            rst = ops.add_bias(rst.reshape(rst.shape[0], H * F), self.bias).view(-1, H, F)
-        rst = rst.mean(-2) if self.last else rst.flatten(-2, -1)
+            rst = ops.add_bias(rst.reshape(-1, H * F), self.bias).view(rst.shape)
+        if self.last and n_mc > 1:
+            rst = torch.stack([r.mean(-2) for r in rst.unbind(0)], 0)     # the head mean of each sample, as the loop's
+        else:
+            rst = rst.mean(-2) if self.last else rst.flatten(-2, -1)
         if self.activation:
             rst = self.activation(rst)
         return (rst, attn.unsqueeze(-1)) if get_attention else rst
