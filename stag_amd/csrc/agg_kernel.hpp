@@ -35,6 +35,7 @@
 #pragma once
 #include "../../include/stag_hip.h"
 #include "noise.hpp"
+#include <stdlib.h>
 
 namespace stag {
 
@@ -115,6 +116,7 @@ struct AggArgs {
   float* ws;               // [n_seg][ws_stride]: D partial sums, then D weight sums if in_norm
   int32_t ws_stride;
   uint32_t ws_bytes;
+  uint32_t idx_bytes;      // extent of indices when it fits a buffer descriptor (< 2^30 edges), else 0
 };
 
 __device__ __forceinline__ void load4(const float* p, int k0, int D, bool vec, float (&v)[4]) {
@@ -724,10 +726,15 @@ struct AggTeam {
   }
 };
 
+// the hot loop of the plain forward launch (agg_plain.hpp): the unit's edges [b, pend) into T.acc
+template <int KIND, int LPE, bool RELU, class TEAM>
+__device__ __forceinline__ void plain_walk(const AggArgs& a, TEAM& T, int b, int pend, int len);
+
 // One unit (a whole row or a segment of a long row) on LPE x SLOTS lanes of a wave:
 // c = this lane's chunk (4 channels) of the channel tile, sl = its edge slot.
+// PLAIN (agg_plain_kernel only): bit 0 = the unit's edges are walked by plain_walk, bit 1 = with relu.
 template <int KIND, int LPE, bool VEC, int PEDGE, int SLOTS, int MULT, int NOUT = 1, bool MC = false, bool WN = false,
-          bool NULLS = false>
+          bool NULLS = false, int PLAIN = 0>
 __device__ __forceinline__ void agg_unit(const AggArgs& a, const int unit, const int c, const int sl,
                                          float (*dp_out)[4] = nullptr) {
   static_assert(LPE * SLOTS <= 64 && 64 % (LPE * SLOTS) == 0, "a unit's lanes stay inside one wave");
@@ -822,7 +829,10 @@ __device__ __forceinline__ void agg_unit(const AggArgs& a, const int unit, const
   const int pend = b + len;
   EdgeIdx<NB> I;
   EdgeRows<NB, PEDGE> R;
-  {
+  if constexpr (PLAIN != 0) {
+    static_assert(SLOTS == 1 && MULT == 1 && NOUT == 1 && PEDGE == 0 && VEC && BLK == 2, "the plain forward launch");
+    plain_walk<KIND, LPE, (PLAIN & 2) != 0>(a, T, b, pend, len);
+  } else {
     // the next block's edge records are fetched while this block's rows are in flight: one
     // round trip per block on the unit's critical path instead of two.  Narrow shapes only
     // (their launch is latency-bound: -2..3 us); at LPE >= 32 the extra registers would cost
@@ -1211,6 +1221,28 @@ hipError_t agg_launch(const AggArgs& a, bool vec, hipStream_t stream);
 #ifndef STAG_AGG_LDS_BYTES
 #define STAG_AGG_LDS_BYTES 0
 #endif
+// The conditions under which a launch is the plain forward launch.  (pedge: agg_launch_impl's parameter family; the
+// log-scale flag only matters to derivatives — the scalar scale arrives exponentiated.)
+inline bool plain_launch_ok(const AggArgs& a, bool vec, int pedge) {
+  return vec && pedge == 0 && a.pmode == STAG_PARAM_SCALAR && !a.outx[0] && !a.dp_part && !a.mc && a.out &&
+         !a.src_scale && !a.in_norm && !a.nidx && (a.relu & ~(kFlagRelu | kFlagLogScale)) == 0 &&
+         (a.wide & 1) == 0 && a.x_bytes != 0 && a.idx_bytes != 0;
+}
+
+// Launch the plain kernel of one noise kind (agg_plain.hpp; defined in agg_plain_<kind>.hip, so that the instantiations
+// compile in parallel with the general ones); a: the arguments agg_launch_shape completed (walk, grid).
+template <int KIND>
+void agg_launch_plain(const AggArgs& a, int lpe, bool walk, dim3 grid, hipStream_t s);
+
+// STAG_AGG_PLAIN=0 in the environment keeps every launch on the general kernel (read at each launch)
+inline bool plain_enabled() {
+#if defined(STAG_TRACE) || defined(STAG_EXP_NO_ROWS)
+  return false;            // the per-unit timestamps and the launch without its row gathers live in the general kernel
+#endif
+  const char* e = getenv("STAG_AGG_PLAIN");
+  return !(e && e[0] == '0' && e[1] == 0);
+}
+
 // the SMALL instantiation of the plain plan-order launch at 32 lanes per row (heavy_slots_of)
 template <int KIND>
 inline void agg_launch_small(const AggArgs& a_in, bool vec, int tiles, hipStream_t s) {
@@ -1319,6 +1351,13 @@ inline void agg_launch_shape(const AggArgs& a_in, bool vec, int pedge, int tiles
     if (pedge == 2) {       // [E, D] parameters: a row per edge
       if (vec) hipLaunchKernelGGL((agg_kernel<KIND, LPE, true, 2, 1, false, false, true>), grid, block, STAG_AGG_LDS_BYTES, s, a);
       else     hipLaunchKernelGGL((agg_kernel<KIND, LPE, false, 2, 1, false, false, true>), grid, block, STAG_AGG_LDS_BYTES, s, a);
+      return;
+    }
+  }
+  if constexpr (KIND >= kNormal && (LPE == 32 || LPE == 64)) {
+    // the plain forward launch has its own kernel (agg_plain.hpp): same sums, fewer instructions
+    if (plain_launch_ok(a, vec, pedge) && plain_enabled()) {
+      agg_launch_plain<KIND>(a, LPE, walk, grid, s);
       return;
     }
   }

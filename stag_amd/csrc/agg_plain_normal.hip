@@ -1,0 +1,9 @@
+// agg_plain_normal.hip — instantiations of agg_plain_kernel for noise kind "normal" (see agg_plain.hpp).
+#include "agg_plain.hpp"
+
+namespace stag {
+template <>
+void agg_launch_plain<kNormal>(const AggArgs& a, int lpe, bool walk, dim3 grid, hipStream_t stream) {
+  agg_launch_plain_impl<kNormal>(a, lpe, walk, grid, stream);
+}
+}  // namespace stag

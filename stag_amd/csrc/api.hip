@@ -817,6 +817,7 @@ static int agg_common(const stag_csr* csr, const stag_plan* plan, const float* x
     const bool w_narrow = wbytes < (1ull << 32) && csr->n_edges < (1 << 24) && (uint64_t)D * 4u < (1u << 24);
     a.wide = (x_narrow ? 0 : 1) | (w_narrow ? 0 : 2);
     a.x_bytes = x_narrow ? (uint32_t)(ldx == 0 ? (uint64_t)D * 4u : xbytes) : 0u;
+    a.idx_bytes = csr->n_edges < (1 << 30) ? (uint32_t)csr->n_edges * 4u : 0u;
   }
   const bool logs = spec->kind == STAG_NOISE_NORMAL && spec->p1_log;
   a.p0 = spec->p0; a.p1 = spec->p1; a.p0s = spec->p0_scalar; a.p1s = logs ? expf(spec->p1_scalar) : spec->p1_scalar;

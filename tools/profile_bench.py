@@ -78,7 +78,7 @@ def counters(out, kernel_sub):
     disp = set()
     name = None
     for row in csv.DictReader(open(f)):
-        if kernel_sub not in row["Kernel_Name"]:
+        if not any(s in row["Kernel_Name"] for s in kernel_sub):
             continue
         name = row["Kernel_Name"]
         disp.add(row["Dispatch_Id"])
@@ -112,14 +112,15 @@ def main():
     os.makedirs(dst, exist_ok=True)
     common = ["--noise", args.noise, "--feat", str(args.feat), "--graph", args.graph,
               "--seg-len", str(args.seg_len), "--workload", args.workload, "--no-cpu-baseline", "--no-variants"]   # one workload per profile
-    kernel_sub = "gat_fwd" if args.workload == "gat" else "agg_kernel"
+    # (the plain forward launch of a kind that draws runs agg_plain_kernel: csrc/agg_plain.hpp)
+    kernel_sub = ("gat_fwd",) if args.workload == "gat" else ("agg_kernel", "agg_plain_kernel")
 
     out, line = run_prof("stats", ["--kernel-trace", "--stats"], ["--steps", "200", "--warmup", "20", *common], scratch)
     stats = find(out, "kernel_stats.csv")
     rows = list(csv.DictReader(open(stats)))
     with open(os.path.join(dst, f"bench_{args.tag}_kernel_stats.csv"), "w") as f:
         f.write(open(stats).read())
-    agg = [r for r in rows if kernel_sub in r["Name"]]
+    agg = [r for r in rows if any(s in r["Name"] for s in kernel_sub)]
     print("kernel stats:", [(r["Name"][:60], r["Calls"], r["AverageNs"]) for r in agg])
     if line:
         with open(os.path.join(dst, f"bench_{args.tag}.json"), "w") as f:
