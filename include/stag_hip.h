@@ -439,6 +439,28 @@ int stag_agg_max_bwd(const stag_csr* csr_t, const stag_plan* plan_t, const float
                      float* dx, float* dw, int64_t ldw, float* dp0_rows, float* dp1_rows, int64_t ldd,
                      void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- half-typed feature rows (a layer under torch.autocast hands over a bf16 / fp16 h = x @ W), additive in v19 ----
+ * stag_agg_fwd with the gathered rows in fp16 or bf16, as they are — no widened copy, half the bytes per gathered row:
+ *     out[v, k] = dscale[v] * sum_{p in row v} w[p, k] * sscale[u_p] * float(x[u_p, k])
+ *   x: [n_src, ldx] of x_dtype (STAG_DTYPE_F16 | STAG_DTYPE_BF16), ldx in ELEMENTS; widening is exact, accumulation and
+ *   out are fp32.  w: 1 (NONE) or the draw of stag_agg_fwd at the same counters (NORMAL | UNIFORM | BERNOULLI with
+ *   SCALAR | PER_CHANNEL parameters, optional relu; pos_base, chunk_base, epoch and csr.nidx as there): a lane owns 8
+ *   channels and draws the two Philox blocks they belong to, so the weights are the fp32 launch's bit for bit.
+ *   dscale, sscale, reduce, `plan` (may be NULL) as for stag_agg_fwd; csr.eid is not read.  Segments of long rows leave
+ *   fp32 partial sums in plan->workspace (>= stag_plan_workspace_bytes(n_seg, D, 0)), added in segment order
+ *   (Kahan-compensated, as the sums inside long units are) by a second small launch: no atomics, results are
+ *   run-to-run bit-identical.  seg_counters are not used; plan->xcd_order is ignored (plan order), which changes no bit.
+ *   STAG_ENOSYS — the caller widens the rows and calls stag_agg_fwd: D % 8 != 0; ldx % 8 != 0 or x not 16-byte
+ *   aligned; ldx == 0 (a broadcast row); in_norm; EXPLICIT weights; PER_EDGE1 / PER_EDGE parameters; p1_log; a launch
+ *   across a 2^32 boundary of the global position.  STAG_EINVAL: a NULL csr / x / spec / out; D <= 0; 0 < ldx < D;
+ *   ldo < D; unknown x_dtype, kind or reduce; deriv != 0; the counter bounds of stag_agg_fwd; a plan without units.
+ *   STAG_ENOMEM: workspace too small.  Every argument is checked before any device work.                          */
+#define STAG_DTYPE_F16 1
+#define STAG_DTYPE_BF16 2
+int stag_agg_fwd_half(const stag_csr* csr, const stag_plan* plan, const void* x, int32_t x_dtype, int64_t ldx,
+                      int32_t D, const stag_noise_spec* spec, int32_t reduce, const float* src_scale,
+                      const float* dst_scale, float* out, int64_t ldo, void* stream);
+
 /* w[eid, k] for every edge of the shard: what the reference keeps in
  * `self._edge_weight_sample` (stag/layers.py:107). relu and in_norm applied.
  * plan (may be NULL): the units bound what one team walks, so a hub row does not serialise.

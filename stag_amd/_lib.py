@@ -18,6 +18,7 @@ _SO = os.environ.get("STAG_HIP_SO") or os.path.join(_HERE, "libstag_hip.so")
 NOISE_NONE, NOISE_EXPLICIT, NOISE_NORMAL, NOISE_UNIFORM, NOISE_BERNOULLI = range(5)
 PARAM_SCALAR, PARAM_PER_CHANNEL, PARAM_PER_EDGE1, PARAM_PER_EDGE = range(4)
 REDUCE_SUM, REDUCE_MEAN = 0, 1
+DTYPE_F16, DTYPE_BF16 = 1, 2   # STAG_DTYPE_* (stag_agg_fwd_half)
 GAT_BWD_ROWDOT, GAT_BWD_SOURCE, GAT_BWD_DER = 1, 2, 4   # STAG_GAT_BWD_* (stag_gat_bwd_stages)
 HEAVY_LEN = 16   # STAG_HEAVY_LEN (include/stag_hip.h)
 XCD_HEADER, XCD_STRIPES, XCD_FINE_MAX = 32, 8, 16   # STAG_XCD_HEADER, STAG_XCD_STRIPES, STAG_XCD_FINE_MAX
@@ -209,6 +210,8 @@ def bind(path):
     l.stag_agg_max_bwd_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
     l.stag_agg_max_bwd.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_int32,
                                    C.POINTER(NoiseSpec), _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, C.c_size_t, _vp]
+    l.stag_agg_fwd_half.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, C.c_int32, C.c_int64, C.c_int32,
+                                    C.POINTER(NoiseSpec), C.c_int32, _vp, _vp, _vp, C.c_int64, _vp]
     if l.stag_abi_version() != 19:
         raise StagHipError("libstag_hip.so ABI version mismatch")
     return l

@@ -1,0 +1,385 @@
+// agg_half.hip — stag_agg_fwd_half: the fused draw-and-aggregate pass over fp16 / bf16 feature rows (gfx950).
+//
+//   out[v, k] = dscale[v] * sum_p w[p, k] * sscale[u_p] * float(x[u_p, k])        fp32 accumulation, fp32 output
+//
+// What a layer under torch.autocast hands the aggregation is a half-typed h = x @ W; widened to fp32 before the launch
+// it costs a streaming cast pass, an fp32 copy and a gather of E rows at 4 bytes per channel.  Here the rows are
+// gathered as they are: a lane owns EIGHT consecutive channels — one 16-byte buffer load per edge, half the bytes of
+// the fp32 kernels' row — widens them in registers (bf16: a shift or a mask; fp16: v_cvt_f32_f16; both exact) and
+// draws the two Philox blocks its channels belong to (chunks chunk_base + 2c and + 2c + 1 of include/stag_hip.h's
+// noise stream: the same w[e, k] bits as an fp32 launch with the same spec).  A row takes D / 8 lanes, a team is the
+// next power of two of that (8 ... 64 lanes); channels past 512 go to further channel tiles (blockIdx.y).
+// The launch walks the plan's units in plan order (one team per unit; no plan: one unit per row).  Edges are taken in
+// blocks (2 with a draw, 4 without), a block's terms are summed from zero and folded into the unit's sum in order,
+// Kahan-compensated once the unit is longer than 16 edges (AggTeam::fold_into's rule).  A segment of a long row
+// leaves its fp32 partial in the plan's workspace; a second small launch (one workgroup per long row) adds every long
+// row's partials — Kahan sums of groups of 16 in segment order, then of the group sums in group order — and applies
+// the row scale.  No atomics, no arrival counters: two launches with the same inputs give the same bits.  agg_kernel / agg_plain_kernel are not touched: they are tuned to the VGPR.
+#include "agg_half.hpp"
+#include "agg_kernel.hpp"   // load4 / store4, kKahanMinLen, u32x4_t (read-only helpers)
+
+namespace stag {
+namespace {
+
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+
+// edges fetched together by a team: the draws of a block run while its rows are in flight
+template <int KIND>
+constexpr int half_blk() { return KIND == kNone ? 4 : 2; }
+
+// the 8 channels of one 16-byte piece of a row, widened exactly
+template <int DT>
+__device__ __forceinline__ void widen8(const u32x4_t t, float (&v)[8]) {
+  const uint32_t wd[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if constexpr (DT == STAG_DTYPE_BF16) {
+      v[2 * i] = __uint_as_float(wd[i] << 16);
+      v[2 * i + 1] = __uint_as_float(wd[i] & 0xFFFF0000u);
+    } else {
+      const f16x2_t h = __builtin_bit_cast(f16x2_t, wd[i]);
+      v[2 * i] = (float)h.x;
+      v[2 * i + 1] = (float)h.y;
+    }
+  }
+}
+
+__device__ __forceinline__ void store8(float* p, int k0, int D, bool vec, const float (&v)[8]) {
+  const float lo[4] = {v[0], v[1], v[2], v[3]}, hi[4] = {v[4], v[5], v[6], v[7]};
+  store4(p, k0, D, vec, lo);
+  store4(p, k0 + 4, D, vec, hi);
+}
+
+// the unit a team serves (plan order; no plan: unit i = row i); false past the end
+template <int LPE>
+__device__ __forceinline__ bool half_unit(const HalfArgs& a, int& row, int& start, int& len, int& slot) {
+  const int64_t rec = (int64_t)blockIdx.x * (256 / LPE) + threadIdx.x / LPE;
+  if (rec >= a.n_units) return false;
+  if (a.units) {
+    const int4 q = *reinterpret_cast<const int4*>(a.units + rec);
+    slot = q.w;
+    row = slot >= 0 ? a.long_rows[q.x] : q.x;
+    start = q.y;
+    len = q.z;
+  } else {
+    row = (int)rec;
+    start = a.indptr[row];
+    len = a.indptr[row + 1] - start;
+    slot = -1;
+  }
+  return true;
+}
+
+__device__ __forceinline__ float row_scale(const HalfArgs& a, int v, int deg) {
+  float dv = a.dst_scale ? a.dst_scale[v] : 1.0f;
+  if (a.mean) dv *= __builtin_amdgcn_rcpf((float)(deg > 1 ? deg : 1));
+  return dv;
+}
+
+template <int KIND, int DT, int LPE>
+__global__ __launch_bounds__(256) void agg_half_fwd_kernel(const HalfArgs a) {
+  constexpr int BLK = half_blk<KIND>();
+  const int c = blockIdx.y * LPE + threadIdx.x % LPE;   // the lane's group of 8 channels
+  const int k0 = 8 * c;
+  int row, start, len, slot;
+  if (k0 >= a.D || !half_unit<LPE>(a, row, start, len, slot)) return;
+  const PhiloxKey key = resolve_epoch(a.key);
+  const uint32_t koff = (uint32_t)k0 * 2u;
+  const bool narrow = a.x_bytes != 0;
+  const __amdgpu_buffer_rsrc_t rx =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+  // the two Philox blocks of the lane's channels: chunks chunk_base + 2c, + 2c + 1 (word 1: chunk | hi32(gpos) << 20)
+  const uint32_t c1a = (a.chunk_base + 2u * (uint32_t)c) | (a.pos_hi << 20);
+  const uint32_t c1b = (a.chunk_base + 2u * (uint32_t)c + 1u) | (a.pos_hi << 20);
+  [[maybe_unused]] float pa[2][4], pb[2][4];
+  if constexpr (KIND >= kNormal) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const bool row_p = a.pmode == STAG_PARAM_PER_CHANNEL;
+      pa[q >> 2][q & 3] = row_p ? a.p0[k0 + q] : a.p0s;
+      pb[q >> 2][q & 3] = row_p ? (a.p1 ? a.p1[k0 + q] : 0.f) : a.p1s;
+    }
+  }
+  const bool kahan = len > kKahanMinLen;
+  float acc[8], comp[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) acc[q] = comp[q] = 0.f;
+  const int end = start + len;
+  for (int p0 = start; p0 < end; p0 += BLK) {
+    int u[BLK];
+    uint32_t nn[BLK];
+    float xs[BLK];
+    u32x4_t xr[BLK];
+#pragma unroll
+    for (int j = 0; j < BLK; ++j) {
+      const int p = p0 + j;
+      if (p < end) {
+        u[j] = a.indices[p];
+        nn[j] = a.pos_lo + (uint32_t)(a.nidx ? a.nidx[p] : p);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < BLK; ++j) {
+      if (p0 + j < end) {
+        if (narrow) {
+          xr[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(__umul24((uint32_t)u[j], a.ldxb) + koff), 0, 0);
+        } else {
+          const char* r = static_cast<const char*>(a.x) + (uint64_t)(uint32_t)u[j] * a.ldxb + koff;
+          xr[j] = *reinterpret_cast<const u32x4_t*>(r);
+        }
+        if (a.src_scale) xs[j] = a.src_scale[u[j]];
+      }
+    }
+    // all the block's draws first: they need nothing from memory and run while its rows are in flight
+    [[maybe_unused]] float w[BLK][2][4];
+    if constexpr (KIND >= kNormal) {
+#pragma unroll
+      for (int j = 0; j < BLK; ++j) {
+        if (p0 + j < end) {
+          draw4<KIND>(nn[j], c1a, key, pa[0], pb[0], a.nflags, w[j][0]);
+          draw4<KIND>(nn[j], c1b, key, pa[1], pb[1], a.nflags, w[j][1]);
+        }
+      }
+    }
+    float t[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) t[q] = 0.f;
+#pragma unroll
+    for (int j = 0; j < BLK; ++j) {
+      if (p0 + j < end) {
+        float xv[8];
+        widen8<DT>(xr[j], xv);
+        if (a.src_scale) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) xv[q] *= xs[j];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          if constexpr (KIND == kNone) t[q] += xv[q];
+          else t[q] = __builtin_fmaf(w[j][q >> 2][q & 3], xv[q], t[q]);
+        }
+      }
+    }
+    if (kahan) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const float y = t[q] - comp[q];
+        const float n = acc[q] + y;
+        comp[q] = (n - acc[q]) - y;
+        acc[q] = n;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) acc[q] += t[q];
+    }
+  }
+  if (slot >= 0) {   // a segment: its partial, added by agg_half_merge_kernel
+    store8(a.ws + (int64_t)slot * a.D, k0, a.D, a.ovec != 0, acc);
+    return;
+  }
+  const float dv = row_scale(a, row, len);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) acc[q] *= dv;
+  store8(a.out + (int64_t)row * a.ldo, k0, a.D, a.ovec != 0, acc);
+}
+
+// One workgroup per long row (a hub row has hundreds of segments: one team adding them one after the other is a chain
+// of dependent loads — 39 us for the 13,000-edge hub of the arxiv-shaped graph).  The two-level form of
+// two_level_sum (agg_kernel.hpp): Kahan sums of GROUPS of kCombineGroup partials in segment order, one group per team
+// and round, then team 0 folds the group sums in group order — a group's Kahan residual joins the second level's
+// compensation.  Groups are cut by segment index alone, so the arithmetic does not depend on the teams per workgroup
+// (the row's width), only on the row's segments.
+template <int LPE>
+__global__ __launch_bounds__(256) void agg_half_merge_kernel(const HalfArgs a) {
+  constexpr int T = 256 / LPE, kAhead = 8;
+  __shared__ float part[T][2][LPE * 8];          // a round's group sums and what they still owe (16 KB)
+  const int r = blockIdx.x, team = threadIdx.x / LPE, lane = threadIdx.x % LPE;
+  const int k0 = 8 * (blockIdx.y * LPE + lane);
+  const bool live = k0 < a.D;                    // (no early return: the workgroup meets at barriers)
+  const int row = a.long_rows[r];
+  const int s0 = a.long_seg_ptr[r], s1 = a.long_seg_ptr[r + 1];
+  const bool vec = a.ovec != 0;
+  float sum[8], comp[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) sum[q] = comp[q] = 0.f;
+  for (int g0 = s0; g0 < s1; g0 += kCombineGroup * T) {   // uniform over the workgroup
+    const int gs = g0 + team * kCombineGroup;
+    if (live && gs < s1) {
+      const int ge = min(gs + kCombineGroup, s1);
+      float gsum[8], gres[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) gsum[q] = gres[q] = 0.f;
+      for (int s = gs; s < ge; s += kAhead) {
+        float t[kAhead][2][4];
+#pragma unroll
+        for (int j = 0; j < kAhead; ++j) {
+          if (s + j < ge) {
+            const float* ws = a.ws + (int64_t)(s + j) * a.D;
+            load4(ws, k0, a.D, vec, t[j][0]);
+            load4(ws, k0 + 4, a.D, vec, t[j][1]);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < kAhead; ++j) {
+          if (s + j < ge) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+              const float y = t[j][q >> 2][q & 3] - gres[q];
+              const float n = gsum[q] + y;
+              gres[q] = (n - gsum[q]) - y;
+              gsum[q] = n;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 8; ++q) { part[team][0][lane * 8 + q] = gsum[q]; part[team][1][lane * 8 + q] = gres[q]; }
+    }
+    __syncthreads();
+    if (team == 0 && live) {
+      for (int j = 0; j < T && g0 + j * kCombineGroup < s1; ++j) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          comp[q] += part[j][1][lane * 8 + q];             // true group sum = its sum - its residual
+          const float y = part[j][0][lane * 8 + q] - comp[q];
+          const float n = sum[q] + y;
+          comp[q] = (n - sum[q]) - y;
+          sum[q] = n;
+        }
+      }
+    }
+    __syncthreads();                                       // the next round overwrites the group sums
+  }
+  if (team != 0 || !live) return;
+  const float dv = row_scale(a, row, a.indptr[row + 1] - a.indptr[row]);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) sum[q] = (sum[q] - comp[q]) * dv;
+  store8(a.out + (int64_t)row * a.ldo, k0, a.D, vec, sum);
+}
+
+int half_lanes_for(int D) {
+  const int n8 = D / 8;
+  int lpe = 8;
+  while (lpe < n8 && lpe < 64) lpe <<= 1;
+  return lpe;
+}
+
+#define STAG_HALF_LPE(F, lpe, ...)                 \
+  do {                                             \
+    switch (lpe) {                                 \
+      case 64: F(64, __VA_ARGS__); break;          \
+      case 32: F(32, __VA_ARGS__); break;          \
+      case 16: F(16, __VA_ARGS__); break;          \
+      default: F(8, __VA_ARGS__); break;           \
+    }                                              \
+  } while (0)
+
+template <int KIND>
+void half_fwd_kind(const HalfArgs& a, int dtype, int lpe, dim3 grid, hipStream_t s) {
+#define STAG_HALF_FWD(L, DT) hipLaunchKernelGGL((agg_half_fwd_kernel<KIND, DT, L>), grid, dim3(256), 0, s, a)
+  if (dtype == STAG_DTYPE_BF16) STAG_HALF_LPE(STAG_HALF_FWD, lpe, STAG_DTYPE_BF16);
+  else STAG_HALF_LPE(STAG_HALF_FWD, lpe, STAG_DTYPE_F16);
+#undef STAG_HALF_FWD
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+}  // namespace
+
+hipError_t half_fwd_launch(const HalfArgs& a, int kind, int dtype, int32_t n_seg, hipStream_t s) {
+  const int lpe = half_lanes_for(a.D);
+  const int T = 256 / lpe;
+  const int tiles = (a.D / 8 + lpe - 1) / lpe;
+  const dim3 grid((unsigned)(((int64_t)a.n_units + T - 1) / T), tiles);
+  if (grid.x > 0) {
+    switch (kind) {
+      case kNone: half_fwd_kind<kNone>(a, dtype, lpe, grid, s); break;
+      case kNormal: half_fwd_kind<kNormal>(a, dtype, lpe, grid, s); break;
+      case kUniform: half_fwd_kind<kUniform>(a, dtype, lpe, grid, s); break;
+      default: half_fwd_kind<kBernoulli>(a, dtype, lpe, grid, s); break;
+    }
+  }
+  if (n_seg > 0 && a.n_long > 0) {
+    const dim3 mg(a.n_long, tiles);                      // one workgroup per long row and channel tile
+#define STAG_HALF_MERGE(L, _) hipLaunchKernelGGL((agg_half_merge_kernel<L>), mg, dim3(256), 0, s, a)
+    STAG_HALF_LPE(STAG_HALF_MERGE, lpe, 0);
+#undef STAG_HALF_MERGE
+  }
+  return hipGetLastError();
+}
+
+}  // namespace stag
+
+using namespace stag;
+
+extern "C" int stag_agg_fwd_half(const stag_csr* csr, const stag_plan* plan, const void* x, int32_t x_dtype, int64_t ldx,
+                                 int32_t D, const stag_noise_spec* spec, int32_t reduce, const float* src_scale,
+                                 const float* dst_scale, float* out, int64_t ldo, void* stream) {
+  // every decision below is taken before any device work
+  if (!csr || !x || !spec || !out) return STAG_EINVAL;
+  if (csr->n_dst < 0 || csr->n_src < 0 || csr->n_edges < 0 || csr->n_edges > 0x7FFFFFFFll || !csr->indptr ||
+      (csr->n_edges > 0 && !csr->indices))
+    return STAG_EINVAL;
+  if (D <= 0 || ldx < 0 || (ldx > 0 && ldx < D) || ldo < D) return STAG_EINVAL;
+  if (x_dtype != STAG_DTYPE_F16 && x_dtype != STAG_DTYPE_BF16) return STAG_EINVAL;
+  if (spec->kind < STAG_NOISE_NONE || spec->kind > STAG_NOISE_BERNOULLI) return STAG_EINVAL;
+  if (reduce != STAG_REDUCE_SUM && reduce != STAG_REDUCE_MEAN) return STAG_EINVAL;
+  if (spec->deriv != 0) return STAG_EINVAL;
+  if (spec->chunk_base < 0 || spec->chunk_base >= (1 << 20)) return STAG_EINVAL;
+  if (spec->p1_log != 0 && (spec->p1_log != 1 || spec->kind != STAG_NOISE_NORMAL)) return STAG_EINVAL;
+  const bool drawn = spec->kind >= STAG_NOISE_NORMAL;
+  if (drawn) {
+    if (!counter_space_ok(spec->pos_base, csr->n_edges, spec->chunk_base, ((int64_t)D + 3) / 4)) return STAG_EINVAL;
+    if (spec->param_mode < STAG_PARAM_SCALAR || spec->param_mode > STAG_PARAM_PER_EDGE) return STAG_EINVAL;
+    if (spec->param_mode == STAG_PARAM_PER_CHANNEL && (!spec->p0 || (spec->kind != STAG_NOISE_BERNOULLI && !spec->p1)))
+      return STAG_EINVAL;
+  }
+  const bool use_plan = plan && plan->n_units > 0;
+  if (use_plan && (!plan->units || !aligned16(plan->units) || plan->n_seg < 0 || plan->n_long < 0)) return STAG_EINVAL;
+  // what the cast route (x.float(), stag_agg_fwd) keeps
+  if (D % 8 != 0 || ldx == 0 || ldx % 8 != 0 || !aligned16(x)) return STAG_ENOSYS;
+  if (spec->in_norm || spec->kind == STAG_NOISE_EXPLICIT || spec->p1_log) return STAG_ENOSYS;
+  if (drawn && spec->param_mode > STAG_PARAM_PER_CHANNEL) return STAG_ENOSYS;
+  if (drawn && ((uint64_t)spec->pos_base & 0xFFFFFFFFull) + (uint64_t)csr->n_edges > (1ull << 32))
+    return STAG_ENOSYS;                                                    // as stag_agg_fwd: one 2^32 range per call
+  int32_t n_seg = 0;
+  if (use_plan && plan->n_seg > 0) {
+    if (!plan->long_rows || !plan->long_seg_ptr || !plan->workspace) return STAG_EINVAL;
+    if (plan->workspace_bytes < stag_plan_workspace_bytes(plan->n_seg, D, 0)) return STAG_ENOMEM;
+    n_seg = plan->n_seg;
+  }
+  if (csr->n_dst == 0) return STAG_OK;
+
+  HalfArgs a{};
+  a.indptr = csr->indptr; a.indices = csr->indices; a.nidx = csr->nidx;   // (csr->eid: nothing here is indexed by edge id)
+  a.n_rows = csr->n_dst; a.D = D;
+  a.x = x; a.ldxb = (uint32_t)(ldx * 2);
+  {
+    // 32-bit byte offsets and 24-bit multiplies behind a buffer descriptor when they reach every row, else 64-bit addresses
+    const uint64_t xbytes = csr->n_src > 0 ? ((uint64_t)(csr->n_src - 1) * (uint64_t)ldx + (uint64_t)D) * 2u : 0u;
+    const bool narrow = xbytes > 0 && xbytes < (1ull << 32) && csr->n_src < (1 << 24) && (uint64_t)ldx * 2u < (1u << 24);
+    a.x_bytes = narrow ? (uint32_t)xbytes : 0u;
+    if (!narrow && (uint64_t)ldx * 2u >= (1ull << 32)) return STAG_ENOSYS;   // a row stride past 32 bits of bytes
+  }
+  a.pmode = drawn ? spec->param_mode : 0;
+  a.nflags = spec->relu ? kFlagRelu : 0;
+  a.p0 = spec->p0; a.p1 = spec->p1; a.p0s = spec->p0_scalar; a.p1s = spec->p1_scalar;
+  a.key.k0 = (uint32_t)(spec->seed & 0xFFFFFFFFull); a.key.k1 = (uint32_t)(spec->seed >> 32);
+  a.key.o0 = (uint32_t)(spec->offset & 0xFFFFFFFFull); a.key.o1 = (uint32_t)(spec->offset >> 32);
+  a.key.epoch = spec->epoch;
+  a.pos_lo = (uint32_t)((uint64_t)spec->pos_base & 0xFFFFFFFFull);
+  a.pos_hi = (uint32_t)((uint64_t)spec->pos_base >> 32);
+  a.chunk_base = (uint32_t)spec->chunk_base;
+  a.src_scale = src_scale; a.dst_scale = dst_scale; a.mean = reduce == STAG_REDUCE_MEAN;
+  a.n_units = csr->n_dst;
+  if (use_plan) {   // plan->xcd_order is ignored: the units are walked in plan order
+    a.units = plan->units; a.n_units = plan->n_units;
+    if (n_seg > 0) {
+      a.long_rows = plan->long_rows; a.long_seg_ptr = plan->long_seg_ptr; a.n_long = plan->n_long;
+      a.ws = plan->workspace;
+    }
+  }
+  a.out = out; a.ldo = ldo;
+  a.ovec = aligned16(out) && ldo % 4 == 0 && (n_seg == 0 || aligned16(plan->workspace));
+  return half_fwd_launch(a, spec->kind, x_dtype, n_seg, (hipStream_t)stream) == hipSuccess ? STAG_OK : STAG_EIO;
+}

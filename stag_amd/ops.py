@@ -174,6 +174,31 @@ def _agg_raw(csrv, x, D, spec, reduce, src_scale, dst_scale, seg_len, want_norm_
     return out, ns
 
 
+_HALF_DTYPES = {torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
+
+
+def _agg_half_raw(csrv, x, D, spec, reduce, src_scale, dst_scale, seg_len, plan_t=None):
+    """One stag_agg_fwd_half launch on csrv: x [n_src, D] fp16 | bf16 as it is (unit column stride, any row stride the
+    entry point takes), out [n_dst, D] fp32.  Bound through ctypes only; the plan is walked in plan order."""
+    spec = _targs_or_c(spec)
+    dev = _lib.require_device(x, csrv.indptr, src_scale, dst_scale)
+    out = torch.empty((csrv.n_dst, D), dtype=torch.float32, device=dev)
+    if csrv.n_dst == 0:
+        return out
+    if plan_t is None:
+        plan_t = csrv.plan(seg_len)
+    nbytes = _lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], D, 0) if plan_t is not None else 0
+    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t, width=None)
+    cs = csrv.struct()
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_agg_fwd_half(
+            C.byref(cs), C.byref(plan_c) if plan_c is not None else None, _lib.ptr(x), _HALF_DTYPES[x.dtype],
+            x.stride(0), D, C.byref(spec), reduce, _lib.ptr(src_scale), _lib.ptr(dst_scale), _lib.ptr(out), D,
+            _lib.stream_of(dev))
+    _lib.check(rc, "stag_agg_fwd_half")
+    return out
+
+
 def _targs_to_ctypes(t):
     """The torch-op argument tuple as a ctypes stag_noise_spec (for the entry points bound through ctypes)."""
     ni, nu, nf, p0, p1, epoch = t
@@ -336,7 +361,11 @@ class _NodeLinear(torch.autograd.Function):
 
     SPLIT = 64
 
+    # Under torch.autocast the products below would come out half-typed and hand the backward a half-typed gradient
+    # for fp32 saved operands (a dtype error in its GEMMs): the transform behind an aggregation stays fp32 — the
+    # aggregated rows are fp32 whatever the gathered rows were (stag_agg_fwd_half).  Outside autocast: no effect.
     @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, x, w, bias=None, add=None):
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
@@ -348,6 +377,7 @@ class _NodeLinear(torch.autograd.Function):
         return torch.addmm(bias, x, w) if bias is not None else x @ w
 
     @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g):
         x, w = ctx.saved_tensors
         # g @ w^T as an NN product on a transposed copy of w (64 KB): 75 against 92 us for the NT form at
@@ -675,6 +705,16 @@ def _bwd_w_raw(csrv, x, g, D, src_scale, broadcast_x=False, spec=None, reduce_k=
 class _Aggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, graph, noise, reduce, src_scale, dst_scale, seg_len, broadcast_x):
+        if half_rows_ok(x, w, noise, broadcast_x, graph):
+            # fp16 / bf16 rows as they are (stag_agg_fwd_half).  The backward is the fp32 launch on csr_t below: grad_out
+            # is fp32, autograd casts dx to x.dtype, and nothing half-typed is saved
+            D = x.shape[1]
+            out = _agg_half_raw(graph.csr, x, D, _noise_spec(noise) if noise is not None else _none_spec(), reduce,
+                                src_scale, dst_scale, seg_len)
+            ctx.graph, ctx.noise, ctx.reduce, ctx.seg_len = _owner(graph), noise, reduce, seg_len
+            ctx.broadcast_x, ctx.D = False, D
+            ctx.save_for_backward(None, None, src_scale, dst_scale, None)
+            return out
         x = _f32c(x)
         D = x.shape[1]
         csrv = graph.csr
@@ -950,6 +990,9 @@ def aggregate(graph, x, weight=None, reduce="sum", src_scale=None, dst_scale=Non
     if not (torch.is_grad_enabled() and (x.requires_grad or (w is not None and w.requires_grad))):
         # nothing to differentiate: straight to the library (no autograd node; host time of a call matters on
         # launch-bound graphs)
+        if half_rows_ok(x, w, noise, _broadcast_x, graph):     # fp16 / bf16 rows as they are: no widened copy
+            return _agg_half_raw(graph.csr, x, D, _noise_spec(noise) if noise is not None else _none_spec(),
+                                 _REDUCE[reduce], _f32c(src_scale), _f32c(dst_scale), seg_len)
         xin, x = x, _f32c(x)
         if (PAD_CONSTANT_INPUTS and D % 4 and D >= PAD_MIN_WIDTH and w is None and not _broadcast_x and x is xin and x.is_cuda
                 and not x.requires_grad and (noise is None or noise.param_mode <= _lib.PARAM_PER_CHANNEL)):
@@ -973,6 +1016,53 @@ def aggregate(graph, x, weight=None, reduce="sum", src_scale=None, dst_scale=Non
 
 # ---- the max reducer (DGL's fn.max; GraphSAGE 'pool', stag/zoo/graph_sage.py:90-93) --------------------------------
 FUSED_MAX = True          # stag_agg_max_fwd / _bwd | the composed route (messages formed, scatter-amax): tests compare both
+# stag_agg_fwd_half on fp16 / bf16 rows | x.float() + stag_agg_fwd.  True because, at the arxiv shape (D = 128, bf16 rows,
+# us per call, profiles/r07/half_rows.txt), it is not slower than the cast route for any kind — none 68.8 against 117.4,
+# Bernoulli 106.7 / 118.1, Uniform 102.5 / 118.6, Normal 115.5 / 117.8; two repeats of the cast route differ by 0.4-0.7.
+# (On the L2-resident PPI batch at D = 256 the drawn kinds lose 12-13 us to the cast route's XCD-aware walk: DESIGN.md 4.5, 5.)
+HALF_ROWS = True
+
+
+def half_rows_why_not(x, w, noise, broadcast_x, graph=None):
+    """The first reason ops.aggregate keeps the cast route (x.float(), stag_agg_fwd) for this call, or None: the launch
+    goes to stag_agg_fwd_half on x as it is.  One clause per refusal of the entry point (include/stag_hip.h) and per
+    path that has no half form (Monte-Carlo batches, parameter gradients, shards, a traced graph)."""
+    if not HALF_ROWS:
+        return "switch"
+    if x.dtype not in _HALF_DTYPES:
+        return "dtype"
+    if broadcast_x:
+        return "broadcast row"
+    if w is not None:
+        return "explicit weights"
+    if x.dim() != 2 or x.shape[1] % 8 != 0:
+        return "width"
+    if x.stride(1) != 1 or x.stride(0) % 8 != 0 or x.stride(0) == 0:
+        return "strides"
+    if noise is not None:
+        if noise.kind < _lib.NOISE_NORMAL or noise.param_mode > _lib.PARAM_PER_CHANNEL:
+            return "noise parameters"
+        if noise.in_norm:
+            return "in-norm"
+        if noise.p1_log or noise.deriv:
+            return "log-scale"
+        if noise.n_samples != 1:
+            return "monte-carlo"
+        if noise.grad_params is not None and any(torch.is_tensor(p) and p.requires_grad for p in noise.grad_params):
+            return "parameter gradients"
+    if getattr(graph, "is_shard", False) or (noise is not None and getattr(noise.graph, "is_shard", False)):
+        return "shard"
+    if torch.compiler.is_compiling():
+        return "compiling"
+    if not x.is_cuda:
+        return "device"
+    if x.data_ptr() % 16 != 0:
+        return "alignment"
+    return None
+
+
+def half_rows_ok(x, w, noise, broadcast_x, graph=None):
+    return half_rows_why_not(x, w, noise, broadcast_x, graph) is None
 
 
 def _max_fwd_raw(csrv, x, D, spec, seg_len, want_cnt, broadcast_x=False):
