@@ -310,6 +310,34 @@ int stag_csr_build(const int32_t* src, const int32_t* dst, int32_t n_src, int32_
                    int64_t n_edges, int32_t* indptr, int32_t* indices, int32_t* eid,
                    int32_t* out_deg, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- graph preprocessing on the device: a node order with L2 locality (additive in v19) -----------------------
+ * The graphs the reference trains on (Cora ... ogbn-arxiv, Reddit) have community structure but arbitrary node ids:
+ * their stripe locality (stag_stripe_locality) is the 1/8 of a random graph and the XCD-aware order has nothing to
+ * hold on to.  stag_reorder_locality proposes a renumbering of a SQUARE graph from its two views (csr: destination-
+ * major; csr_t: source-major; only indptr / indices are read):
+ *   coordinates  x[v, j], j < dims (a multiple of 4, 4 ... 32), fp32, uniform in [-1, 1): x = 2 u - 1 with u the
+ *                UNIFORM draw of the noise stream at position v, chunk j / 4, offset 0 and this seed;
+ *   rounds       smoothing rounds on the symmetrised graph, double-buffered:
+ *                x'[v] = (x[v] + sum_in x[u] + sum_out x[w]) / (1 + indeg + outdeg), in-edges in csr position order,
+ *                then out-edges in csr_t position order; after each round every column is centred and divided by its
+ *                standard deviation (a fixed-order two-level reduction; a column whose deviation is zero — a variance
+ *                below 1e-10 of its mean square — is left alone);
+ *   key          bit (dims - 1 - j) of key[v] = x[v, j] > 0;
+ *   order        a stable radix sort of (key, node id): perm[new id] = old id, inv[old id] = new id.
+ * No float atomics, no order that depends on scheduling: perm is a pure function of the graph, dims, rounds and seed.
+ * A long row is walked by one team of dims / 4 lanes (this is preprocessing, not the hot path).
+ * workspace >= stag_reorder_workspace_bytes(n, n_edges, dims), 16-byte aligned.  STAG_EINVAL: a NULL csr / csr_t /
+ * perm / inv, dims outside the above, rounds < 0, csr->n_dst != csr->n_src, a csr_t of other sizes, a NULL indptr
+ * (indices with edges); STAG_ENOMEM: workspace NULL or too small; n == 0: STAG_OK.  Checked before any device work.
+ * stag_relabel_edges: src_out[e] = inv[src[e]], dst_out[e] = inv[dst[e]] — the edge list of the renumbered graph,
+ * edge ids unchanged (ids must be valid indices of inv: the caller's graph guarantees it).                        */
+size_t stag_reorder_workspace_bytes(int32_t n, int64_t n_edges, int32_t dims);
+int stag_reorder_locality(const stag_csr* csr, const stag_csr* csr_t, int32_t dims, int32_t rounds, uint64_t seed,
+                          int32_t* perm /* [n] new -> old */, int32_t* inv /* [n] old -> new */, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int stag_relabel_edges(const int32_t* src, const int32_t* dst, int64_t n_edges, const int32_t* inv, int32_t* src_out,
+                       int32_t* dst_out, void* stream);
+
 /* ---- test hook: raw Philox words, out[n_pos][n_chunk][4] ------------------ */
 int stag_philox_raw(uint64_t seed, uint64_t offset, int64_t pos0, int64_t n_pos,
                     int32_t n_chunk, uint32_t* out, void* stream);

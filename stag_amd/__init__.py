@@ -7,7 +7,7 @@ Drop-in for the hot path of yuanqing-wang/stag: the `stag.layers` /
 from . import distributions, function, layers, likelihoods, models, utils, zoo  # noqa: F401
 from . import random  # noqa: F401
 from .graph import (Graph, add_reverse_edges, add_self_loop, batch, graph, mean_nodes,  # noqa: F401
-                    rand_graph, remove_self_loop, sum_nodes)
+                    rand_graph, remove_self_loop, reorder_graph, sum_nodes)
 from .noise import EdgeNoise  # noqa: F401
 from .random import manual_seed  # noqa: F401
 

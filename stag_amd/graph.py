@@ -125,6 +125,8 @@ def xcd_graph_ranges(edge_cuts, rows, width, range_bytes=None, stripes=None, fin
 class CsrView:
     """Tensors of one CSR plus the ctypes struct the library takes."""
 
+    original_rows = None     # forward view of reorder_graph(noise="original"): (row pointers of the original graph, node_perm)
+
     def __init__(self, n_dst, n_src, indptr, indices, eid=None, nidx=None):
         self.n_dst, self.n_src = int(n_dst), int(n_src)
         self._short = None
@@ -646,7 +648,27 @@ class Graph:
                   None if self._batch_num_nodes is None else self._batch_num_nodes.to(device))
         g.ndata = {k: v.to(device) for k, v in self.ndata.items()}
         g.edata = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in self.edata.items()}
+        if self.node_perm is not None:
+            _carry_reorder(self, g, device)
         return g
+
+    # ---- a reordered graph (reorder_graph below) -----------------------------------
+    node_perm = None       # [N] int64, new id -> old id; None: an ordinary graph
+    node_inv = None        # [N] int64, old id -> new id
+    noise_keying = None    # "original" | "own"
+
+    def rows_from_original(self, t):
+        """Rows of a per-node tensor of the graph this one was reordered from, in this graph's order (plain indexing:
+        differentiable)."""
+        if self.node_perm is None:
+            raise ValueError("not a reordered graph (stag_amd.reorder_graph)")
+        return t[self.node_perm]
+
+    def rows_to_original(self, t):
+        """Rows of a per-node tensor of this graph in the order of the graph it was reordered from."""
+        if self.node_inv is None:
+            raise ValueError("not a reordered graph (stag_amd.reorder_graph)")
+        return t[self.node_inv]
 
     def __repr__(self):
         return f"Graph(num_nodes={self._n}, num_edges={self.number_of_edges()}, device={self.device})"
@@ -845,6 +867,9 @@ def _batch_build(graphs):
     dev = graphs[0].device
     sizes = [g._n for g in graphs]
     n_edges = [int(g._src.shape[0]) for g in graphs]
+    if any(g.node_perm is not None for g in graphs):
+        # (the concatenated views have no forward nidx: the union would silently draw other noise than its parts)
+        raise ValueError("batch() over a reordered graph (stag_amd.reorder_graph) is not supported")
     total = int(sum(sizes))
     node_off = np.concatenate([[0], np.cumsum(sizes[:-1])]).astype(np.int64) if graphs else np.zeros(0, np.int64)
     E = int(sum(n_edges))
@@ -968,6 +993,121 @@ def _concat_csr(graphs, node_off, n_edges, node_off_per_edge, total, jobs=None, 
         nidx = (torch.cat([v.nidx for v in parts]) + e_off_per_edge) if name == "csr_t" else None
         views.append(CsrView(total, total, indptr, indices, eid, nidx))
     return views
+
+
+# ---- node reordering ------------------------------------------------------------------------------------------
+# Every kernel gathers x[u] for the sources of a destination row, and the XCD-aware order (XCD_ORDER above) keeps those
+# rows in one XCD's L2 only when sources lie near their destinations in the ROW ORDER.  A block-diagonal batch has that by
+# construction; a citation graph has communities but arbitrary ids.  reorder_graph renumbers the nodes — and, because the
+# noise of an edge is keyed by a position that stag_csr.nidx may name freely, the renumbered graph returns the rows of
+# the original graph bit for bit, in the new order, with the same seeds (noise="original").
+#
+# Limits: transforms (add_self_loop, remove_self_loop, add_reverse_edges) return an ORDINARY graph — reorder last.
+# GraphShard / ChannelShard built from a reordered graph's edges key the noise by their own positions.  GAT weight
+# gradients that leave the fused backward as an [E, H] tensor (explicit weights with requires_grad, vi=True parameters)
+# are not available under noise="original" (ops._gat_bwd_reordered); noise="own" has them.
+def _locality_perm(g, dims, rounds, seed):
+    """(perm, inv) int32 device tensors of stag_reorder_locality on g's two views."""
+    N, E, dev = g._n, g.number_of_edges(), g.device
+    perm = torch.empty(N, dtype=torch.int32, device=dev)
+    inv = torch.empty(N, dtype=torch.int32, device=dev)
+    if N == 0:
+        return perm, inv
+    lib, a, b = _lib.lib(), g.csr, g.csr_t
+    nbytes = lib.stag_reorder_workspace_bytes(N, E, int(dims))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        rc = lib.stag_reorder_locality(C.byref(a.struct()), C.byref(b.struct()), int(dims), int(rounds),
+                                       int(seed) & (2 ** 64 - 1), _lib.ptr(perm), _lib.ptr(inv), _lib.ptr(ws), nbytes,
+                                       _lib.stream_of(dev))
+    _lib.check(rc, "stag_reorder_locality")
+    return perm, inv
+
+
+def _relabel(g, inv):
+    """g's edge list with both ends mapped through inv (old -> new): stag_relabel_edges on the device."""
+    E = g.number_of_edges()
+    if not g._src.is_cuda or E == 0:
+        return inv[g._src.long()].to(torch.int32), inv[g._dst.long()].to(torch.int32)
+    inv32 = inv.to(torch.int32).contiguous()
+    src, dst = torch.empty_like(g._src), torch.empty_like(g._dst)
+    with _lib.on_device(g.device):
+        _lib.check(_lib.lib().stag_relabel_edges(_lib.ptr(g._src), _lib.ptr(g._dst), E, _lib.ptr(inv32), _lib.ptr(src),
+                                                 _lib.ptr(dst), _lib.stream_of(g.device)), "stag_relabel_edges")
+    return src, dst
+
+
+def _original_keying(g, new):
+    """Both views of `new` (g relabelled) with nidx = the position the same edge has in g.csr: a row of either graph holds
+    its edges in ascending edge id, so a row's terms arrive in the same order with the same draws.  The forward view
+    also keeps g's row pointers and the permutation for ops._gat_bwd_reordered."""
+    N, E, dev = g._n, g.number_of_edges(), g.device
+    pos_of_eid = torch.empty(E, dtype=torch.int32, device=dev)
+    if E:
+        pos_of_eid[g.csr.eid.long()] = torch.arange(E, dtype=torch.int32, device=dev)
+    views = []
+    for s, d in ((new._src, new._dst), (new._dst, new._src)):
+        indptr, indices, eid = build_csr(s, d, N, N)
+        views.append(CsrView(N, N, indptr, indices, eid, pos_of_eid[eid.long()].contiguous()))
+    new._csr, new._csr_t = views
+    new._csr.original_rows = (g.csr.indptr, new.node_perm)
+
+
+def _carry_reorder(g, new, device):
+    """Graph.to(): the permutation and the keying of a reordered graph go with it."""
+    new.node_perm, new.node_inv, new.noise_keying = g.node_perm.to(device), g.node_inv.to(device), g.noise_keying
+    if g.noise_keying == "original":
+        move = lambda v: CsrView(v.n_dst, v.n_src, v.indptr.to(device), v.indices.to(device), v.eid.to(device), v.nidx.to(device))
+        new._csr, new._csr_t = move(g.csr), move(g.csr_t)
+        new._csr.original_rows = (g.csr.original_rows[0].to(device), new.node_perm)
+
+
+def reorder_graph(g, node_permute_algo="locality", permute_config=None, store_ids=True, dims=16, rounds=8, seed=0,
+                  noise="original"):
+    """`dgl.reorder_graph` for node order: g's edges with both ends relabelled; EDGE IDS DO NOT CHANGE (edata, explicit
+    [E, .] weights and per-edge parameters apply as they are).
+
+    node_permute_algo  "locality": stag_reorder_locality (include/stag_hip.h) on a device graph — smoothed random
+                       coordinates (dims, rounds, seed) and a sign hash; "custom": permute_config["nodes_perm"], a
+                       tensor [N], new id -> old id (CPU or device graphs).
+    noise              "original": both views carry nidx = the position of the same edge in g.csr, so every seeded
+                       result on the new graph is the one on g, row for row, bit for bit; "own": the graph is keyed by
+                       its own positions (csr.nidx is None: the plain launch stays eligible).
+    Every ndata tensor with N rows is row-permuted; store_ids puts the permutation under ndata["_ID"].  The result has
+    node_perm / node_inv (int64) and rows_from_original(t) = t[perm] / rows_to_original(t) = t[inv]."""
+    if node_permute_algo not in ("locality", "custom"):
+        raise ValueError(f"unknown node_permute_algo {node_permute_algo!r}: 'locality' or 'custom'")
+    if noise not in ("original", "own"):
+        raise ValueError(f"unknown noise keying {noise!r}: 'original' or 'own'")
+    if g.batch_size > 1:
+        raise ValueError("a batched graph is block-diagonal already: reorder its parts before batch()")
+    N, dev = g._n, g.device
+    if node_permute_algo == "custom":
+        perm = None if permute_config is None else permute_config.get("nodes_perm")
+        if perm is None:
+            raise ValueError("node_permute_algo='custom' needs permute_config={'nodes_perm': tensor[N]}")
+        perm = torch.as_tensor(perm)
+        if perm.dim() != 1 or perm.shape[0] != N or perm.is_floating_point() or perm.dtype == torch.bool or not torch.equal(
+                torch.sort(perm.to(torch.int64)).values.cpu(), torch.arange(N, dtype=torch.int64)):
+            raise ValueError("nodes_perm is not a permutation of range(N)")
+        perm = perm.to(device=dev, dtype=torch.int64)
+        inv = torch.empty_like(perm)
+        inv[perm] = torch.arange(N, dtype=torch.int64, device=dev)
+    else:
+        if dev.type != "cuda":
+            raise _lib.StagHipError("node_permute_algo='locality' runs on a HIP device only (graph on %s); there is no CPU "
+                                    "path" % dev)
+        perm, inv = (t.to(torch.int64) for t in _locality_perm(g, dims, rounds, seed))
+    src, dst = _relabel(g, inv)
+    new = Graph(src, dst, N, _trusted=True)
+    new.node_perm, new.node_inv, new.noise_keying = perm, inv, noise
+    if noise == "original":
+        _original_keying(g, new)
+    new.ndata = {k: (v[perm] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == N else v) for k, v in g.ndata.items()}
+    new.edata = dict(g.edata)
+    if store_ids:
+        new.ndata["_ID"] = perm
+    return new
 
 
 def _readout(g, name, reduce):

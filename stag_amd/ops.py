@@ -1695,6 +1695,9 @@ def _gat_bwd_fused(csrv, csrt, el, er, ft, stats, G, out, H, F, neg_slope, spec,
     if not (_GAT_BWD_FUSED and E > 0 and gat_cooperative_shape(H, F, seg_len)
             and (one or (lph & (lph - 1)) == 0)):      # the two-pass form wants F / 4 a power of two
         return None
+    if csrv.original_rows is not None:
+        return _gat_bwd_reordered(csrv, csrt, el, er, ft, stats, G, out, H, F, neg_slope, _targs_or_c(spec), nscale, want_dw,
+                                  seg_len, dev, attn_drop, want_dp)
     plan_f, plan_b = csrv.plan(seg_len, need=True), csrt.plan(seg_len, need=True)
     if _torch_ext.available() and not want_dp and (_GAT_BWD_ONE_GATHER or attn_drop is not None):
         # the dispatcher op (csrc/torch_ext.cpp: stag::gat_bwd): same library call, visible to a compiled graph
@@ -1804,6 +1807,40 @@ class _GatBwdStages:
 
     def der(self):
         self._call(self.plan_b, _lib.GAT_BWD_DER)
+
+
+def _gat_bwd_reordered(csrv, csrt, el, er, ft, stats, G, out, H, F, neg_slope, spec, nscale, want_dw, seg_len, dev,
+                       attn_drop, want_dp):
+    """The one-gather GAT backward on a graph of reorder_graph(noise="original").  stag_gat_bwd uses csr_t.nidx twice: as
+    the noise index of an edge and as the slot its d s goes to, and step 3 (d er) expects a row's slots to be contiguous
+    — on such a graph nidx names positions of the ORIGINAL graph, where they are contiguous in the original's rows.  So
+    the stages run one at a time (stag_gat_bwd_stages): the row dots and the source pass on this graph, step 3 over the
+    original graph's row pointers (no plan: a unit per row), and d er comes back through the permutation.  The stages
+    return no [E, H] weight gradient and no parameter gradients."""
+    if want_dw or want_dp:
+        raise NotImplementedError("GAT weight / noise-parameter gradients on a graph reordered with noise='original': "
+                                  "reorder with noise='own'")
+    indptr0, perm = csrv.original_rows
+    n = csrv.n_dst
+    d_el = torch.empty((n, H), dtype=torch.float32, device=dev)
+    d_er0 = torch.empty((n, H), dtype=torch.float32, device=dev)
+    d_ft = torch.empty((n, H, F), dtype=torch.float32, device=dev)
+    st = _GatBwdStages(csrv, csrt, el, er, ft, stats, G, out, H, F, neg_slope, spec, nscale, attn_drop, seg_len,
+                       d_el, d_er0, d_ft, dev)
+    st.rowdot()
+    st.source()
+    cs0 = _lib.Csr(n, n, csrv.n_edges, _lib.ptr(indptr0), _lib.ptr(csrv.indices), _lib.ptr(csrv.eid), None)
+    p0 = _lib.Plan.from_buffer_copy(st.pf)
+    p0.n_units = p0.n_long = p0.n_seg = 0          # step 3 then takes a row per thread from cs0.indptr
+    pb, _k = _plan_struct(csrt, seg_len, 1, 0, dev, plan_t=st.plan_b)
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_gat_bwd_stages(
+            C.byref(cs0), C.byref(p0), C.byref(csrt.struct()), C.byref(pb), _lib.ptr(el), _lib.ptr(er), _lib.ptr(ft),
+            _lib.ptr(stats), _lib.ptr(G), _lib.ptr(out), H, F, float(neg_slope), C.byref(spec), _lib.ptr(nscale),
+            C.byref(st.drop) if st.drop is not None else None, _lib.ptr(d_el), _lib.ptr(d_er0), _lib.ptr(d_ft),
+            _lib.ptr(st.scratch), _lib.GAT_BWD_DER, _lib.stream_of(dev))
+    _lib.check(rc, "stag_gat_bwd_stages")
+    return d_el, d_er0[perm], d_ft, None
 
 
 _GAT_VI_FUSED = True       # vi=True parameter gradients inside the GAT kernels (stag_gat_bwd_dp) | materialised [E, H] weights
