@@ -16,6 +16,7 @@
 // row's partials — Kahan sums of groups of 16 in segment order, then of the group sums in group order — and applies
 // the row scale.  No atomics, no arrival counters: two launches with the same inputs give the same bits.  agg_kernel / agg_plain_kernel are not touched: they are tuned to the VGPR.
 #include "agg_half.hpp"
+#include "entry_args.hpp"
 #include "agg_kernel.hpp"   // load4 / store4, kKahanMinLen, u32x4_t (read-only helpers)
 
 namespace stag {
@@ -257,13 +258,6 @@ __global__ __launch_bounds__(256) void agg_half_merge_kernel(const HalfArgs a) {
   store8(a.out + (int64_t)row * a.ldo, k0, a.D, vec, sum);
 }
 
-int half_lanes_for(int D) {
-  const int n8 = D / 8;
-  int lpe = 8;
-  while (lpe < n8 && lpe < 64) lpe <<= 1;
-  return lpe;
-}
-
 #define STAG_HALF_LPE(F, lpe, ...)                 \
   do {                                             \
     switch (lpe) {                                 \
@@ -282,12 +276,10 @@ void half_fwd_kind(const HalfArgs& a, int dtype, int lpe, dim3 grid, hipStream_t
 #undef STAG_HALF_FWD
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 hipError_t half_fwd_launch(const HalfArgs& a, int kind, int dtype, int32_t n_seg, hipStream_t s) {
-  const int lpe = half_lanes_for(a.D);
+  const int lpe = lanes_for(a.D / 8, 8);   // 8 channels per lane
   const int T = 256 / lpe;
   const int tiles = (a.D / 8 + lpe - 1) / lpe;
   const dim3 grid((unsigned)(((int64_t)a.n_units + T - 1) / T), tiles);
@@ -316,10 +308,9 @@ extern "C" int stag_agg_fwd_half(const stag_csr* csr, const stag_plan* plan, con
                                  int32_t D, const stag_noise_spec* spec, int32_t reduce, const float* src_scale,
                                  const float* dst_scale, float* out, int64_t ldo, void* stream) {
   // every decision below is taken before any device work
-  if (!csr || !x || !spec || !out) return STAG_EINVAL;
-  if (csr->n_dst < 0 || csr->n_src < 0 || csr->n_edges < 0 || csr->n_edges > 0x7FFFFFFFll || !csr->indptr ||
-      (csr->n_edges > 0 && !csr->indices))
-    return STAG_EINVAL;
+  int rc = check_csr(csr);
+  if (rc) return rc;
+  if (!x || !spec || !out) return STAG_EINVAL;
   if (D <= 0 || ldx < 0 || (ldx > 0 && ldx < D) || ldo < D) return STAG_EINVAL;
   if (x_dtype != STAG_DTYPE_F16 && x_dtype != STAG_DTYPE_BF16) return STAG_EINVAL;
   if (spec->kind < STAG_NOISE_NONE || spec->kind > STAG_NOISE_BERNOULLI) return STAG_EINVAL;
@@ -334,20 +325,16 @@ extern "C" int stag_agg_fwd_half(const stag_csr* csr, const stag_plan* plan, con
     if (spec->param_mode == STAG_PARAM_PER_CHANNEL && (!spec->p0 || (spec->kind != STAG_NOISE_BERNOULLI && !spec->p1)))
       return STAG_EINVAL;
   }
-  const bool use_plan = plan && plan->n_units > 0;
-  if (use_plan && (!plan->units || !aligned16(plan->units) || plan->n_seg < 0 || plan->n_long < 0)) return STAG_EINVAL;
+  const bool use_plan = plan_in_use(plan);
+  if (use_plan && check_plan_units(plan, kPlanCounts)) return STAG_EINVAL;
   // what the cast route (x.float(), stag_agg_fwd) keeps
   if (D % 8 != 0 || ldx == 0 || ldx % 8 != 0 || !aligned16(x)) return STAG_ENOSYS;
   if (spec->in_norm || spec->kind == STAG_NOISE_EXPLICIT || spec->p1_log) return STAG_ENOSYS;
   if (drawn && spec->param_mode > STAG_PARAM_PER_CHANNEL) return STAG_ENOSYS;
-  if (drawn && ((uint64_t)spec->pos_base & 0xFFFFFFFFull) + (uint64_t)csr->n_edges > (1ull << 32))
-    return STAG_ENOSYS;                                                    // as stag_agg_fwd: one 2^32 range per call
-  int32_t n_seg = 0;
-  if (use_plan && plan->n_seg > 0) {
-    if (!plan->long_rows || !plan->long_seg_ptr || !plan->workspace) return STAG_EINVAL;
-    if (plan->workspace_bytes < stag_plan_workspace_bytes(plan->n_seg, D, 0)) return STAG_ENOMEM;
-    n_seg = plan->n_seg;
-  }
+  rc = check_positions(spec, csr->n_edges, D, drawn);                      // as stag_agg_fwd: one 2^32 range per call
+  if (rc) return rc;
+  const int32_t n_seg = use_plan ? plan->n_seg : 0;
+  if (use_plan && (rc = check_plan_segments(plan, kPlanSegPtr | kPlanWorkspace, stag_plan_workspace_bytes(n_seg, D, 0)))) return rc;
   if (csr->n_dst == 0) return STAG_OK;
 
   HalfArgs a{};
@@ -361,24 +348,9 @@ extern "C" int stag_agg_fwd_half(const stag_csr* csr, const stag_plan* plan, con
     a.x_bytes = narrow ? (uint32_t)xbytes : 0u;
     if (!narrow && (uint64_t)ldx * 2u >= (1ull << 32)) return STAG_ENOSYS;   // a row stride past 32 bits of bytes
   }
-  a.pmode = drawn ? spec->param_mode : 0;
-  a.nflags = spec->relu ? kFlagRelu : 0;
-  a.p0 = spec->p0; a.p1 = spec->p1; a.p0s = spec->p0_scalar; a.p1s = spec->p1_scalar;
-  a.key.k0 = (uint32_t)(spec->seed & 0xFFFFFFFFull); a.key.k1 = (uint32_t)(spec->seed >> 32);
-  a.key.o0 = (uint32_t)(spec->offset & 0xFFFFFFFFull); a.key.o1 = (uint32_t)(spec->offset >> 32);
-  a.key.epoch = spec->epoch;
-  a.pos_lo = (uint32_t)((uint64_t)spec->pos_base & 0xFFFFFFFFull);
-  a.pos_hi = (uint32_t)((uint64_t)spec->pos_base >> 32);
-  a.chunk_base = (uint32_t)spec->chunk_base;
+  fill_spec(a, spec, 0);   // (flags: relu only; a derivative and a log-scale were refused above)
   a.src_scale = src_scale; a.dst_scale = dst_scale; a.mean = reduce == STAG_REDUCE_MEAN;
-  a.n_units = csr->n_dst;
-  if (use_plan) {   // plan->xcd_order is ignored: the units are walked in plan order
-    a.units = plan->units; a.n_units = plan->n_units;
-    if (n_seg > 0) {
-      a.long_rows = plan->long_rows; a.long_seg_ptr = plan->long_seg_ptr; a.n_long = plan->n_long;
-      a.ws = plan->workspace;
-    }
-  }
+  fill_plan(a, csr, plan);   // plan->xcd_order is ignored: the units are walked in plan order
   a.out = out; a.ldo = ldo;
   a.ovec = aligned16(out) && ldo % 4 == 0 && (n_seg == 0 || aligned16(plan->workspace));
   return half_fwd_launch(a, spec->kind, x_dtype, n_seg, (hipStream_t)stream) == hipSuccess ? STAG_OK : STAG_EIO;

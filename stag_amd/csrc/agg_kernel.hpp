@@ -35,6 +35,7 @@
 #pragma once
 #include "../../include/stag_hip.h"
 #include "noise.hpp"
+#include "entry_args.hpp"
 #include <stdlib.h>
 
 namespace stag {
@@ -59,7 +60,7 @@ struct AggArgs {
   const float* p1;
   float p0s, p1s;
   int32_t pmode;   // STAG_PARAM_*
-  int32_t relu, in_norm;   // relu: noise flags = relu | deriv << 1 | log-scale << 3 (noise.hpp)
+  int32_t nflags, in_norm;   // nflags: relu | deriv << 1 | log-scale << 3 (noise.hpp)
   int32_t wgroup;          // EXPLICIT: channels sharing one weight column (<= 1: one per channel)
   PhiloxKey key;
   uint32_t pos_lo, pos_hi;   // lo32 / hi32 of the shard's global position base
@@ -549,7 +550,7 @@ struct AggTeam {
     if constexpr (DRAW_FIRST) {
 #pragma unroll
       for (int j = m * BLK; j < (m + 1) * BLK; ++j)
-        if (p0 + j < pend) draw4<KIND>(I.nn[j], c1, key, pa, pb, a.relu, wb[j - m * BLK]);
+        if (p0 + j < pend) draw4<KIND>(I.nn[j], c1, key, pa, pb, a.nflags, wb[j - m * BLK]);
     }
 #else
     constexpr bool DRAW_FIRST = false;
@@ -562,23 +563,23 @@ struct AggTeam {
         [[maybe_unused]] ExtraAcc<NX> dd;          // dd.acc[o] = derivative o of this edge's draw
         [[maybe_unused]] float g0[4], g1[4];        // PEDGE 3: the two derivatives of this edge's draw
         if constexpr (PEDGE == 3) {
-          const float s1 = (a.relu & kFlagLogScale) ? exp_scale(R.P.q1[j]) : R.P.q1[j];
+          const float s1 = (a.nflags & kFlagLogScale) ? exp_scale(R.P.q1[j]) : R.P.q1[j];
 #pragma unroll
           for (int q = 0; q < 4; ++q) { pa[q] = R.P.q0[j]; pb[q] = s1; }
-          draw4_grad<KIND>(I.nn[j], c1, key, pa, pb, a.relu, w, g0, g1);
+          draw4_grad<KIND>(I.nn[j], c1, key, pa, pb, a.nflags, w, g0, g1);
         } else if constexpr (PEDGE == 4) {
-          draw4_grad<KIND>(I.nn[j], c1, key, pa, pb, a.relu, w, g0, g1);
+          draw4_grad<KIND>(I.nn[j], c1, key, pa, pb, a.nflags, w, g0, g1);
         } else if constexpr (DRAW_FIRST) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) w[q] = wb[j - m * BLK][q];
         } else if constexpr (NX == 0) {
           edge_weight(R, I, j, w);
         } else if constexpr (!MC) {
-          draw4_grad<KIND>(I.nn[j], c1, key, pa, pb, a.relu, w, dd.acc[0], dd.acc[1]);
+          draw4_grad<KIND>(I.nn[j], c1, key, pa, pb, a.nflags, w, dd.acc[0], dd.acc[1]);
         } else {
-          draw4<KIND>(I.nn[j], c1, key, pa, pb, a.relu, w);
+          draw4<KIND>(I.nn[j], c1, key, pa, pb, a.nflags, w);
 #pragma unroll
-          for (int o = 0; o < NX; ++o) draw4<KIND>(I.nn[j], c1, KX.k[o], pa, pb, a.relu, dd.acc[o]);
+          for (int o = 0; o < NX; ++o) draw4<KIND>(I.nn[j], c1, KX.k[o], pa, pb, a.nflags, dd.acc[o]);
           if constexpr (WN) {
 #pragma unroll
             for (int o = 0; o < NX; ++o)
@@ -699,29 +700,29 @@ struct AggTeam {
       } else {
         loadrow4(row_at(a.p0, I.ee[j], a.ldwb, koff, (a.wide & 2) != 0), k0, a.D, VEC, w);
       }
-      if (a.relu & kFlagRelu) {
+      if (a.nflags & kFlagRelu) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) w[q] = fmaxf(w[q], 0.0f);
       }
     } else {
       if constexpr (PEDGE == 1) {
-        const float s1 = (a.relu & kFlagLogScale) ? exp_scale(R.P.q1[j]) : R.P.q1[j];
+        const float s1 = (a.nflags & kFlagLogScale) ? exp_scale(R.P.q1[j]) : R.P.q1[j];
 #pragma unroll
         for (int q = 0; q < 4; ++q) { pa[q] = R.P.q0[j]; pb[q] = s1; }
-        draw4<KIND>(I.nn[j], c1, key, pa, pb, a.relu, w);
+        draw4<KIND>(I.nn[j], c1, key, pa, pb, a.nflags, w);
         return;
       } else if constexpr (PEDGE == 2) {
-        if (a.relu & kFlagLogScale) {         // [E, D] log-scales exponentiated where they are used: no [E, D] exp pass
+        if (a.nflags & kFlagLogScale) {         // [E, D] log-scales exponentiated where they are used: no [E, D] exp pass
           float pbe[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) pbe[q] = exp_scale(R.P.pb[j][q]);
-          draw4<KIND>(I.nn[j], c1, key, R.P.pa[j], pbe, a.relu, w);
+          draw4<KIND>(I.nn[j], c1, key, R.P.pa[j], pbe, a.nflags, w);
         } else {
-          draw4<KIND>(I.nn[j], c1, key, R.P.pa[j], R.P.pb[j], a.relu, w);
+          draw4<KIND>(I.nn[j], c1, key, R.P.pa[j], R.P.pb[j], a.nflags, w);
         }
         return;
       }
-      draw4<KIND>(I.nn[j], c1, key, pa, pb, a.relu, w);
+      draw4<KIND>(I.nn[j], c1, key, pa, pb, a.nflags, w);
     }
   }
 };
@@ -1093,7 +1094,7 @@ __device__ __forceinline__ void hoist_args(AggArgs& l) {
   }
   if constexpr (KIND >= kNormal && LPE >= STAG_HOIST_MIN_LPE) {
     STAG_PIN_S(l.eid); STAG_PIN_S(l.nidx);
-    STAG_PIN_S(l.p0); STAG_PIN_S(l.p1); STAG_PIN_S(l.p0s); STAG_PIN_S(l.p1s); STAG_PIN_S(l.pmode); STAG_PIN_S(l.relu);
+    STAG_PIN_S(l.p0); STAG_PIN_S(l.p1); STAG_PIN_S(l.p0s); STAG_PIN_S(l.p1s); STAG_PIN_S(l.pmode); STAG_PIN_S(l.nflags);
     STAG_PIN_S(l.in_norm);
     STAG_PIN_S(l.key.k0); STAG_PIN_S(l.key.k1); STAG_PIN_S(l.key.o0); STAG_PIN_S(l.key.o1); STAG_PIN_S(l.key.epoch);
     STAG_PIN_S(l.pos_lo); STAG_PIN_S(l.pos_hi); STAG_PIN_S(l.chunk_base);
@@ -1225,7 +1226,7 @@ hipError_t agg_launch(const AggArgs& a, bool vec, hipStream_t stream);
 // log-scale flag only matters to derivatives — the scalar scale arrives exponentiated.)
 inline bool plain_launch_ok(const AggArgs& a, bool vec, int pedge) {
   return vec && pedge == 0 && a.pmode == STAG_PARAM_SCALAR && !a.outx[0] && !a.dp_part && !a.mc && a.out &&
-         !a.src_scale && !a.in_norm && !a.nidx && (a.relu & ~(kFlagRelu | kFlagLogScale)) == 0 &&
+         !a.src_scale && !a.in_norm && !a.nidx && (a.nflags & ~(kFlagRelu | kFlagLogScale)) == 0 &&
          (a.wide & 1) == 0 && a.x_bytes != 0 && a.idx_bytes != 0;
 }
 
@@ -1375,9 +1376,7 @@ inline hipError_t agg_launch_impl(const AggArgs& a, bool vec, hipStream_t s) {
   const int nchunk = (a.D + 3) / 4;
   const int pedge = (KIND < kNormal) ? 0 : a.pmode == STAG_PARAM_PER_EDGE1 ? (a.eg0 ? 3 : 1)
                     : a.pmode == STAG_PARAM_PER_EDGE ? 2 : 0;
-  // lanes per unit: smallest power of two covering the row, capped at a wave
-  int lpe = 1;
-  while (lpe < nchunk && lpe < 64) lpe <<= 1;
+  const int lpe = lanes_for(nchunk, 1);   // lanes per unit
   const int tiles = (nchunk + lpe - 1) / lpe;
   switch (lpe) {
     case 64: agg_launch_shape<KIND, 64>(a, vec, pedge, tiles, s); break;

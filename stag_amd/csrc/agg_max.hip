@@ -16,6 +16,7 @@
 // destination's record, redraws w from the forward position (nidx), recomputes m bit for bit and sends g / cnt
 // where m equals the maximum.  Sums run in edge order inside a unit and in segment order across segments.
 #include "agg_max.hpp"
+#include "entry_args.hpp"
 
 namespace stag {
 namespace {
@@ -376,13 +377,6 @@ __global__ __launch_bounds__(256) void agg_max_bwd_merge_kernel(const MaxArgs a)
   }
 }
 
-int lanes_for(int D) {
-  const int nchunk = (D + 3) / 4;
-  int lpe = 1;
-  while (lpe < nchunk && lpe < 64) lpe <<= 1;
-  return lpe;
-}
-
 dim3 unit_grid(const MaxArgs& a, int lpe) {
   const int T = 256 / lpe;
   const int tiles = ((a.D + 3) / 4 + lpe - 1) / lpe;
@@ -427,7 +421,7 @@ bool vec_ok(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
 }  // namespace
 
 hipError_t max_fwd_launch(const MaxArgs& a, int32_t n_seg, hipStream_t s) {
-  const int lpe = lanes_for(a.D);
+  const int lpe = lanes_for((a.D + 3) / 4, 1);
   const bool vec = a.D % 4 == 0 && a.ldx % 4 == 0 && a.ldo % 4 == 0 && vec_ok(a.x) && vec_ok(a.out) &&
                    (n_seg == 0 || vec_ok(a.ws));
   const dim3 grid = unit_grid(a, lpe);
@@ -456,7 +450,7 @@ hipError_t max_bwd_launch(const MaxArgs& a, int32_t n_seg, hipStream_t s) {
   const int64_t n_prep = (int64_t)a.n_og_rows * nchunk;
   if (n_prep > 0)
     hipLaunchKernelGGL(agg_max_prep_kernel, dim3((unsigned)((n_prep + 255) / 256)), dim3(256), 0, s, a);
-  const int lpe = lanes_for(a.D);
+  const int lpe = lanes_for((a.D + 3) / 4, 1);
   const bool vec = a.D % 4 == 0 && a.ldx % 4 == 0 && a.ldd % 4 == 0 && vec_ok(a.x) && (!a.dx || vec_ok(a.dx)) &&
                    (!a.dp0 || (vec_ok(a.dp0) && vec_ok(a.dp1))) && (n_seg == 0 || vec_ok(a.ws));
   const dim3 grid = unit_grid(a, lpe);

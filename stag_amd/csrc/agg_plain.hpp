@@ -130,7 +130,7 @@ __attribute__((amdgpu_waves_per_eu(STAG_PLAIN_WAVES, STAG_PLAIN_WAVES))) void ag
   STAG_PIN_S(a.key.k0); STAG_PIN_S(a.key.k1); STAG_PIN_S(a.key.o0); STAG_PIN_S(a.key.o1); STAG_PIN_S(a.key.epoch);
   STAG_PIN_S(a.pos_lo); STAG_PIN_S(a.pos_hi); STAG_PIN_S(a.chunk_base);
   // the launch-uniform facts (plain_launch_ok): constants from here on
-  a.relu = RELU ? kFlagRelu : 0;
+  a.nflags = RELU ? kFlagRelu : 0;
   a.in_norm = 0; a.norm_scale_out = nullptr;
   a.src_scale = nullptr;
   a.nidx = nullptr; a.eid = nullptr;
@@ -168,7 +168,7 @@ __attribute__((amdgpu_waves_per_eu(STAG_PLAIN_WAVES, STAG_PLAIN_WAVES))) void ag
 template <int KIND>
 inline void agg_launch_plain_impl(const AggArgs& a, int lpe, bool walk, dim3 grid, hipStream_t s) {
   const dim3 block(STAG_BLOCK_THREADS);
-  const bool relu = (a.relu & kFlagRelu) != 0;
+  const bool relu = (a.nflags & kFlagRelu) != 0;
 #define STAG_PLAIN_GO(L, R, W) hipLaunchKernelGGL((agg_plain_kernel<KIND, L, R, W>), grid, block, STAG_AGG_LDS_BYTES, s, a)
   if (lpe == 32) {
     if (walk) { if (relu) STAG_PLAIN_GO(32, true, true); else STAG_PLAIN_GO(32, false, true); }

@@ -20,8 +20,10 @@
 
 #include "../../include/stag_hip.h"
 #include "agg_kernel.hpp"
+#include "entry_args.hpp"
 
 namespace {
+using stag::aligned16;
 using stag::load4;
 using stag::team_sum;
 
@@ -456,7 +458,6 @@ __global__ __launch_bounds__(256) void normal_kl_bwd_kernel(const float* loc, co
         (s_w[0][threadIdx.x] + s_w[1][threadIdx.x]) + (s_w[2][threadIdx.x] + s_w[3][threadIdx.x]);
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline int lpe_for(int K, int CT) {
   int lpe = 8;
   while (lpe * 4 < K && lpe < 64) lpe <<= 1;

@@ -1,6 +1,6 @@
-// api.hip — the C ABI of include/stag_hip.h: argument checks, host-side launch
-// planning, and the auxiliary kernels (noise materialisation, weight gradient,
-// readout, raw Philox test hook).  The hot kernel lives in agg_kernel.hpp.
+// api.hip — the C ABI of include/stag_hip.h: entry points (a csr, a spec and a plan are checked and translated by
+// entry_args.hpp; an entry point adds what only it asks for), host-side launch planning, and the auxiliary kernels
+// (noise materialisation, weight gradient, readout, raw Philox test hook).  The hot kernel lives in agg_kernel.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -9,6 +9,7 @@
 #include "../../include/stag_hip.h"
 #include "agg_kernel.hpp"
 #include "agg_max.hpp"
+#include "entry_args.hpp"
 
 using namespace stag;
 
@@ -18,49 +19,6 @@ hipError_t agg_launch(const AggArgs& a, bool vec, hipStream_t stream);
 }
 
 namespace {
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// n_edges: per-edge arrays (explicit weights, [E, 1 | Dn] parameters) of a graph without edges have no address.
-// Dn: the noise width, whose chunks must fit the counter word's chunk field (0: not known here)
-int check_spec(const stag_noise_spec* s, int64_t n_edges = 1, int32_t Dn = 0) {
-  if (!s) return STAG_EINVAL;
-  if (s->kind < STAG_NOISE_NONE || s->kind > STAG_NOISE_BERNOULLI) return STAG_EINVAL;
-  if (s->kind == STAG_NOISE_EXPLICIT && !s->p0 && n_edges > 0) return STAG_EINVAL;
-  if (s->deriv < 0 || s->deriv > 2 || s->chunk_base < 0 || s->chunk_base >= (1 << 20)) return STAG_EINVAL;
-  if (s->deriv != 0 && (s->in_norm || (s->kind != STAG_NOISE_NORMAL && s->kind != STAG_NOISE_UNIFORM)))
-    return STAG_EINVAL;   // only reparameterised draws have a derivative; in-norm is not differentiated here
-  if (s->p1_log != 0 && (s->p1_log != 1 || s->kind != STAG_NOISE_NORMAL)) return STAG_EINVAL;   // a log-scale is a Normal's
-  if (s->p1_log && s->param_mode == STAG_PARAM_PER_CHANNEL) return STAG_ENOSYS;   // exponentiate a [Dn] row yourself
-  if (s->kind >= STAG_NOISE_NORMAL) {
-    if (!counter_space_ok(s->pos_base, n_edges, s->chunk_base, ((int64_t)Dn + 3) / 4)) return STAG_EINVAL;
-    if (s->param_mode < STAG_PARAM_SCALAR || s->param_mode > STAG_PARAM_PER_EDGE) return STAG_EINVAL;
-    const bool per_edge = s->param_mode == STAG_PARAM_PER_EDGE1 || s->param_mode == STAG_PARAM_PER_EDGE;
-    if (s->param_mode != STAG_PARAM_SCALAR && !(per_edge && n_edges == 0)) {
-      if (!s->p0) return STAG_EINVAL;
-      if (s->kind != STAG_NOISE_BERNOULLI && !s->p1) return STAG_EINVAL;
-    }
-  }
-  return STAG_OK;
-}
-
-int check_csr(const stag_csr* g) {
-  if (!g || g->n_dst < 0 || g->n_src < 0 || g->n_edges < 0) return STAG_EINVAL;
-  if (g->n_edges > 0x7FFFFFFFll) return STAG_EINVAL;   // int32 CSR positions
-  if (!g->indptr) return STAG_EINVAL;
-  if (g->n_edges > 0 && !g->indices) return STAG_EINVAL;
-  return STAG_OK;
-}
-
-PhiloxKey make_key(const stag_noise_spec* s) {
-  PhiloxKey k;
-  k.k0 = (uint32_t)(s->seed & 0xFFFFFFFFull);
-  k.k1 = (uint32_t)(s->seed >> 32);
-  k.o0 = (uint32_t)(s->offset & 0xFFFFFFFFull);
-  k.o1 = (uint32_t)(s->offset >> 32);
-  k.epoch = s->epoch;
-  return k;
-}
 
 // ------------------------------------------------------------------------- //
 __global__ void philox_raw_kernel(PhiloxKey key, int64_t pos0, int64_t n_pos, int n_chunk,
@@ -765,10 +723,8 @@ int stag_philox_raw(uint64_t seed, uint64_t offset, int64_t pos0, int64_t n_pos,
   if (!out || n_pos < 0 || n_chunk <= 0 || !aligned16(out)) return STAG_EINVAL;
   const int64_t n = n_pos * n_chunk;
   if (n == 0) return STAG_OK;
-  stag_noise_spec s{};
-  s.seed = seed; s.offset = offset;
   hipLaunchKernelGGL(philox_raw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, make_key(&s), pos0, n_pos, n_chunk, out);
+                     (hipStream_t)stream, make_key(seed, offset, nullptr), pos0, n_pos, n_chunk, out);
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
@@ -819,22 +775,12 @@ static int agg_common(const stag_csr* csr, const stag_plan* plan, const float* x
     a.x_bytes = x_narrow ? (uint32_t)(ldx == 0 ? (uint64_t)D * 4u : xbytes) : 0u;
     a.idx_bytes = csr->n_edges < (1 << 30) ? (uint32_t)csr->n_edges * 4u : 0u;
   }
-  const bool logs = spec->kind == STAG_NOISE_NORMAL && spec->p1_log;
-  a.p0 = spec->p0; a.p1 = spec->p1; a.p0s = spec->p0_scalar; a.p1s = logs ? expf(spec->p1_scalar) : spec->p1_scalar;
-  a.pmode = spec->kind >= STAG_NOISE_NORMAL ? spec->param_mode : 0;
-  a.relu = (spec->relu ? kFlagRelu : 0) | (spec->deriv << kDerivShift) | (logs ? kFlagLogScale : 0);
+  fill_spec(a, spec, spec->deriv);
   a.in_norm = spec->in_norm;
   a.wgroup = (spec->kind == STAG_NOISE_EXPLICIT && spec->group > 1) ? spec->group : 1;
   if (a.wgroup > 1 && (D % a.wgroup != 0 || spec->in_norm)) return STAG_EINVAL;
-  a.key = make_key(spec);
-  a.pos_lo = (uint32_t)((uint64_t)spec->pos_base & 0xFFFFFFFFull);
-  a.pos_hi = (uint32_t)((uint64_t)spec->pos_base >> 32);
-  a.chunk_base = (uint32_t)spec->chunk_base;
-  // one launch must not straddle a 2^32 boundary of the global position space (the kernel keeps
-  // hi32 in a scalar and adds pos_lo to the local index in 32 bits, with or without nidx): shards
-  // are < 2^31 edges, so split the call at the boundary
-  if (spec->kind >= STAG_NOISE_NORMAL && (uint64_t)a.pos_lo + (uint64_t)csr->n_edges > (1ull << 32))
-    return STAG_ENOSYS;
+  rc = check_positions(spec, csr->n_edges, D, spec->kind >= STAG_NOISE_NORMAL);
+  if (rc) return rc;
   a.src_scale = src_scale; a.dst_scale = dst_scale; a.mean = (reduce == STAG_REDUCE_MEAN);
   a.out = out; a.ldo = ldo; a.norm_scale_out = norm_scale_out;
   for (int o = 0; o + 1 < nout; ++o) a.outx[o] = extra[o];
@@ -844,37 +790,29 @@ static int agg_common(const stag_csr* csr, const stag_plan* plan, const float* x
     a.dp_part = eg->dp_part;
   }
 
-  const bool use_plan = plan && plan->n_units > 0;
+  const bool use_plan = plan_in_use(plan);
   const bool has_segs = use_plan && plan->n_seg > 0;
-  a.n_units = csr->n_dst;
+  // the XCD-aware order is not for the block partials of stag_agg_bwd_dp: they are added in block order, which stays
+  // the plan's own
+  const bool xcd = use_plan && plan->xcd_order && !(eg && eg->dp_part);
+  // partial rows: [D sums | D weight sums if in-norm], or [nout x D] with extra outputs
+  const size_t need = has_segs ? stag_plan_workspace_bytes(plan->n_seg, nout * D, spec->in_norm) : 0;
+  rc = check_plan(plan, kPlanHeavy | (xcd ? kPlanXcd : 0) | kPlanSegPtr | kPlanWorkspace | kPlanNarrow | kPlanCounters, need);
+  if (rc) return rc;
+  fill_plan(a, csr, plan);
   if (use_plan) {
-    if (!plan->units || !aligned16(plan->units)) return STAG_EINVAL;
-    a.units = a.units_plan = static_cast<const stag_unit*>(plan->units);
-    a.n_units = plan->n_units;
-    if (plan->n_heavy < 0 || plan->n_heavy > plan->n_units) return STAG_EINVAL;
+    a.units_plan = plan->units;
     a.n_heavy = plan->n_heavy;
-    // the XCD-aware order of the same records (stag_plan_xcd).  Not for the block partials of stag_agg_bwd_dp: they
-    // are added in block order, which stays the plan's own
-    if (plan->xcd_order && !(eg && eg->dp_part)) {
-      const int64_t sh = plan->xcd_stride_heavy, sl = plan->xcd_stride_light;
-      if (!aligned16(plan->xcd_order) || sh < 0 || sl < 0 || sh > plan->n_heavy || sl > plan->n_units ||     /* (sl may count heavy units: stag_plan_xcd_ranges with n_heavy = 0) */
-          STAG_XCD_STRIPES * (sh + sl) < plan->n_units || STAG_XCD_STRIPES * (sh + sl) > 0x7FFFFFFFll) return STAG_EINVAL;
+    if (xcd) {
       a.xcd = plan->xcd_order;
-      a.units = reinterpret_cast<const stag_unit*>(plan->xcd_order + STAG_XCD_HEADER);
-      a.walk.sh = (int32_t)sh;     // agg_launch_shape completes the walk for its block size
-      a.walk.sl = (int32_t)sl;
+      a.units = xcd_units(plan);
+      a.walk.sh = plan->xcd_stride_heavy;     // agg_launch_shape completes the walk for its block size
+      a.walk.sl = plan->xcd_stride_light;
     }
   }
   if (has_segs) {
-    if (!plan->long_rows || !plan->long_seg_ptr || !plan->workspace || !plan->seg_counters)
-      return STAG_EINVAL;
-    // partial rows: [D sums | D weight sums if in-norm], or [nout x D] with extra outputs
-    const size_t need = stag_plan_workspace_bytes(plan->n_seg, nout * D, spec->in_norm);
-    if (plan->workspace_bytes < need) return STAG_ENOMEM;
-    a.long_rows = plan->long_rows; a.long_seg_ptr = plan->long_seg_ptr;
-    if (need >= (1ull << 32)) return STAG_ENOSYS;   // partials go through a 32-bit buffer descriptor
-    a.ws = plan->workspace; a.ws_stride = D * nout * (spec->in_norm ? 2 : 1); a.ws_bytes = (uint32_t)need;
-    a.n_long = plan->n_long; a.seg_counters = plan->seg_counters; a.n_seg = plan->n_seg;
+    a.ws_stride = D * nout * (spec->in_norm ? 2 : 1); a.ws_bytes = (uint32_t)need;
+    a.seg_counters = plan->seg_counters; a.n_seg = plan->n_seg;
   }
 
   // dwordx4 path needs 16-B aligned rows everywhere a float4 is formed
@@ -1016,8 +954,7 @@ extern "C" {
 
 static void dp_shape(int32_t D, int64_t n_units, int& lpe, int& tiles, int64_t& gx) {
   const int nchunk = (D + 3) / 4;
-  lpe = 1;
-  while (lpe < nchunk && lpe < 64) lpe <<= 1;
+  lpe = lanes_for(nchunk, 1);
   tiles = (nchunk + lpe - 1) / lpe;
   const int tpb = STAG_BLOCK_THREADS / lpe;
   gx = (n_units + tpb - 1) / tpb;
@@ -1065,17 +1002,6 @@ int stag_agg_bwd_dp(const stag_csr* csr_t, const stag_plan* plan_t, const float*
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
-// plan fields the unit-walking auxiliary kernels need
-static int set_units(NoiseArgs& a, const stag_csr* csr, const stag_plan* plan) {
-  a.n_units = csr->n_dst;
-  if (plan && plan->n_units > 0) {
-    if (!plan->units || !aligned16(plan->units)) return STAG_EINVAL;
-    if (plan->n_seg > 0 && !plan->long_rows) return STAG_EINVAL;
-    a.units = plan->units; a.long_rows = plan->long_rows; a.n_units = plan->n_units;
-  }
-  return STAG_OK;
-}
-
 #define STAG_LPE_DISPATCH(KERNEL, lpe, vec, grid, s, args)                                      \
   do {                                                                                          \
     switch (lpe) {                                                                              \
@@ -1118,19 +1044,14 @@ int stag_noise_materialize(const stag_csr* csr, const stag_plan* plan, const sta
   }
   NoiseArgs a{};
   a.indptr = csr->indptr; a.eid = csr->eid; a.nidx = csr->nidx; a.n_rows = csr->n_dst;
-  a.Dn = Dn; a.kind = spec->kind; a.p0 = spec->p0; a.p1 = spec->p1;
-  const bool logs = spec->kind == STAG_NOISE_NORMAL && spec->p1_log;
-  a.p0s = spec->p0_scalar; a.p1s = logs ? expf(spec->p1_scalar) : spec->p1_scalar;
-  a.pmode = spec->kind >= STAG_NOISE_NORMAL ? spec->param_mode : 0;
-  a.nflags = (spec->relu ? kFlagRelu : 0) | (spec->deriv << kDerivShift) | (logs ? kFlagLogScale : 0);
+  a.Dn = Dn;
+  fill_spec(a, spec, spec->deriv);
   a.in_norm = spec->in_norm;
-  a.key = make_key(spec); a.pos_base = spec->pos_base; a.chunk_base = (uint32_t)spec->chunk_base;
   a.w = w; a.ldw = ldw; a.norm_scale = spec->in_norm ? norm_scale : nullptr;
-  rc = set_units(a, csr, plan);
+  rc = fill_units(a, csr, plan);
   if (rc) return rc;
   const int nchunk = (Dn + 3) / 4;
-  int lpe = 1;
-  while (lpe < nchunk && lpe < 64) lpe <<= 1;
+  const int lpe = lanes_for(nchunk, 1);
   const bool vec = (Dn % 4 == 0) && (ldw % 4 == 0) && aligned16(w) && (!a.norm_scale || aligned16(norm_scale));
   const dim3 grid((a.n_units + 256 / lpe - 1) / (256 / lpe), (nchunk + lpe - 1) / lpe);
   hipStream_t s = (hipStream_t)stream;
@@ -1152,21 +1073,13 @@ int stag_agg_bwd_w(const stag_csr* csr, const stag_plan* plan, const float* x, i
   BwdWArgs b{};
   NoiseArgs& a = b.n;
   a.indptr = csr->indptr; a.eid = csr->eid; a.nidx = csr->nidx; a.n_rows = csr->n_dst; a.Dn = D;
-  if (spec && spec->kind >= STAG_NOISE_NORMAL && (spec->deriv != 0 || dw1)) {
-    a.kind = spec->kind; a.p0 = spec->p0; a.p1 = spec->p1;
-    const bool logs = spec->kind == STAG_NOISE_NORMAL && spec->p1_log;
-    a.p0s = spec->p0_scalar; a.p1s = logs ? expf(spec->p1_scalar) : spec->p1_scalar; a.pmode = spec->param_mode;
-    a.nflags = (spec->relu ? kFlagRelu : 0) | ((dw1 ? 0 : spec->deriv) << kDerivShift) | (logs ? kFlagLogScale : 0);
-    a.key = make_key(spec); a.pos_base = spec->pos_base; a.chunk_base = (uint32_t)spec->chunk_base;
-  }
+  if (spec && spec->kind >= STAG_NOISE_NORMAL && (spec->deriv != 0 || dw1)) fill_spec(a, spec, dw1 ? 0 : spec->deriv);
   a.w = dw; a.ldw = ldw;
-  rc = set_units(a, csr, plan);
+  rc = fill_units(a, csr, plan);
   if (rc) return rc;
   b.indices = csr->indices; b.x = x; b.ldx = ldx; b.g = g; b.ldg = ldg; b.src_scale = src_scale;
   b.reduce_k = reduce_k ? 1 : 0; b.w1 = dw1;
-  const int nchunk = (D + 3) / 4;
-  int lpe = 1;
-  while (lpe < nchunk && lpe < 64) lpe <<= 1;
+  const int lpe = lanes_for((D + 3) / 4, 1);
   bool vec = (D % 4 == 0) && (ldx % 4 == 0) && (ldg % 4 == 0) && aligned16(x) && aligned16(g);
   if (!reduce_k) vec = vec && (ldw % 4 == 0) && aligned16(dw) && (!dw1 || aligned16(dw1));
   if (a.kind >= kNormal && a.pmode == STAG_PARAM_PER_CHANNEL) vec = vec && aligned16(a.p0) && (!a.p1 || aligned16(a.p1));
@@ -1185,8 +1098,7 @@ int stag_segment_reduce(const float* x, int64_t ldx, int32_t D, const int32_t* o
   if (n_seg == 0) return STAG_OK;
   if (!x) return STAG_EINVAL;
   const int nchunk = (D + 3) / 4;
-  int lpe = 1;
-  while (lpe < nchunk && lpe < 64) lpe <<= 1;
+  const int lpe = lanes_for(nchunk, 1);
   const bool vec = (D % 4 == 0) && (ldx % 4 == 0) && (ldo % 4 == 0) && aligned16(x) && aligned16(out);
   const dim3 grid((n_seg + 256 / lpe - 1) / (256 / lpe), (nchunk + lpe - 1) / lpe);
   const int m = reduce == STAG_REDUCE_MEAN ? 1 : 0;
@@ -1267,36 +1179,21 @@ int max_common(const stag_csr* csr, const stag_plan* plan, const float* x, int64
   if (spec->in_norm) return STAG_ENOSYS;                                   // (the composed route keeps it)
   if (spec->kind == STAG_NOISE_EXPLICIT && spec->group > 1) return STAG_ENOSYS;
   if (csr->n_edges > 0 && !x) return STAG_EINVAL;
-  const bool logs = spec->kind == STAG_NOISE_NORMAL && spec->p1_log;
   a = MaxArgs{};
   a.indptr = csr->indptr; a.indices = csr->indices; a.eid = csr->eid; a.nidx = csr->nidx;
   a.n_rows = csr->n_dst; a.D = D; a.x = x; a.ldx = ldx;
-  a.kind = spec->kind;
-  a.pmode = spec->kind >= STAG_NOISE_NORMAL ? spec->param_mode : 0;
-  a.nflags = (spec->relu ? kFlagRelu : 0) | (logs ? kFlagLogScale : 0);
-  a.p0 = spec->p0; a.p1 = spec->p1; a.p0s = spec->p0_scalar; a.p1s = logs ? expf(spec->p1_scalar) : spec->p1_scalar;
-  a.key = make_key(spec); a.pos_base = spec->pos_base; a.chunk_base = (uint32_t)spec->chunk_base;
-  if (spec->kind >= STAG_NOISE_NORMAL && ((uint64_t)spec->pos_base & 0xFFFFFFFFull) + (uint64_t)csr->n_edges > (1ull << 32))
-    return STAG_ENOSYS;                                                    // as stag_agg_fwd: one 2^32 range per call
-  a.n_units = csr->n_dst;
-  n_seg = 0;
-  if (plan && plan->n_units > 0) {
-    if (!plan->units || !aligned16(plan->units) || plan->n_seg < 0 || plan->n_long < 0) return STAG_EINVAL;
-    a.units = plan->units; a.n_units = plan->n_units;
-    if (plan->xcd_order) {
-      const int64_t sh = plan->xcd_stride_heavy, sl = plan->xcd_stride_light;
-      if (!aligned16(plan->xcd_order) || sh < 0 || sl < 0 || sh > plan->n_heavy || sl > plan->n_units ||
-          STAG_XCD_STRIPES * (sh + sl) < plan->n_units || STAG_XCD_STRIPES * (sh + sl) > 0x7FFFFFFFll) return STAG_EINVAL;
-      a.units = reinterpret_cast<const stag_unit*>(plan->xcd_order + STAG_XCD_HEADER);
-      a.xcd = 1; a.sh = (int32_t)sh; a.sl = (int32_t)sl;
-    }
-    if (plan->n_seg > 0) {
-      if (!plan->long_rows || !plan->long_seg_ptr || !plan->workspace) return STAG_EINVAL;
-      if (plan->workspace_bytes < stag_plan_workspace_bytes(plan->n_seg, nws * D, 0)) return STAG_ENOMEM;
-      a.long_rows = plan->long_rows; a.long_seg_ptr = plan->long_seg_ptr; a.n_long = plan->n_long;
-      a.ws = plan->workspace; a.nws = nws;
-      n_seg = plan->n_seg;
-    }
+  fill_spec(a, spec, 0);
+  rc = check_positions(spec, csr->n_edges, D, spec->kind >= STAG_NOISE_NORMAL);
+  if (rc) return rc;
+  rc = check_plan(plan, kPlanCounts | kPlanXcd | kPlanSegPtr | kPlanWorkspace,
+                  plan ? stag_plan_workspace_bytes(plan->n_seg, nws * D, 0) : 0);
+  if (rc) return rc;
+  fill_plan(a, csr, plan);
+  n_seg = plan_in_use(plan) ? plan->n_seg : 0;
+  if (n_seg > 0) a.nws = nws;
+  if (plan_in_use(plan) && plan->xcd_order) {
+    a.units = xcd_units(plan);
+    a.xcd = 1; a.sh = plan->xcd_stride_heavy; a.sl = plan->xcd_stride_light;
   }
   return STAG_OK;
 }

@@ -18,6 +18,7 @@
 // merges the states in segment order: m = max m_i, l = sum l_i e^(m_i-m), acc likewise.
 #include "../../include/stag_hip.h"
 #include "agg_kernel.hpp"
+#include "entry_args.hpp"
 
 using namespace stag;
 
@@ -44,7 +45,7 @@ struct GatArgs {
   const float* p0;
   const float* p1;
   float p0s, p1s;
-  int32_t pmode, relu;
+  int32_t pmode, nflags;   // nflags: relu | log-scale << 3 (noise.hpp)
   PhiloxKey key;
   uint32_t pos_lo, pos_hi;
   float* out;
@@ -95,19 +96,19 @@ __device__ __forceinline__ void head_w4(const GatArgs& a, const PhiloxKey& key, 
       q0 = in ? a.p0[ed * a.H + h] : 0.f;
       q1 = (in && a.p1) ? a.p1[ed * a.H + h] : 0.f;
     }
-    if (a.pmode != STAG_PARAM_SCALAR && (a.relu & kFlagLogScale)) q1 = exp_scale(q1);
+    if (a.pmode != STAG_PARAM_SCALAR && (a.nflags & kFlagLogScale)) q1 = exp_scale(q1);
     pa[j] = q0; pb[j] = q1;
   }
   const uint32_t c1 = chunk | (a.pos_hi << 20);
   switch (a.kind) {
-    case kNormal: draw4<kNormal>(n, c1, key, pa, pb, a.relu, w); break;
-    case kUniform: draw4<kUniform>(n, c1, key, pa, pb, a.relu, w); break;
-    case kBernoulli: draw4<kBernoulli>(n, c1, key, pa, pb, a.relu, w); break;
+    case kNormal: draw4<kNormal>(n, c1, key, pa, pb, a.nflags, w); break;
+    case kUniform: draw4<kUniform>(n, c1, key, pa, pb, a.nflags, w); break;
+    case kBernoulli: draw4<kBernoulli>(n, c1, key, pa, pb, a.nflags, w); break;
     case kExplicit:
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float t = (h0 + j < a.H) ? a.p0[ed * a.H + h0 + j] : 0.f;
-        w[j] = (a.relu & kFlagRelu) ? fmaxf(t, 0.f) : t;
+        w[j] = (a.nflags & kFlagRelu) ? fmaxf(t, 0.f) : t;
       }
       break;
     default: w[0] = w[1] = w[2] = w[3] = 1.0f;
@@ -1810,11 +1811,11 @@ __global__ __launch_bounds__(kBlkThreads) void gat_bwd_one_kernel(const GatBwd1A
           const bool in = h < H;
           float q0 = a.p0s, q1 = a.p1s;
           if (a.pmode == STAG_PARAM_PER_CHANNEL) { q0 = in ? a.p0[h] : 0.f; q1 = (in && a.p1) ? a.p1[h] : 0.f; }
-          if (a.pmode != STAG_PARAM_SCALAR && (a.relu & kFlagLogScale)) q1 = exp_scale(q1);
+          if (a.pmode != STAG_PARAM_SCALAR && (a.nflags & kFlagLogScale)) q1 = exp_scale(q1);
           pa[jj] = q0; pb[jj] = q1;
         }
-        if (a.kind == kNormal) draw4_grad<kNormal>(n, (uint32_t)cc | c1hi, key, pa, pb, a.relu, w, d0, d1);
-        else draw4_grad<kUniform>(n, (uint32_t)cc | c1hi, key, pa, pb, a.relu, w, d0, d1);
+        if (a.kind == kNormal) draw4_grad<kNormal>(n, (uint32_t)cc | c1hi, key, pa, pb, a.nflags, w, d0, d1);
+        else draw4_grad<kUniform>(n, (uint32_t)cc | c1hi, key, pa, pb, a.nflags, w, d0, d1);
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
           const int h = 4 * cc + jj;
@@ -1908,8 +1909,6 @@ __global__ __launch_bounds__(256) void gat_seg_finish_kernel(const float* ws, in
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 // lanes per head of the cooperative kernels: F / 4 rounded up to a power of two (F % 4 == 0)
@@ -1926,21 +1925,22 @@ static int fill_drop(GatArgs& a, const stag_gat_drop* drop) {
   if (!(drop->keep_prob > 0.0f)) return STAG_EINVAL;
   a.drop_keep = drop->keep_prob;
   a.drop_scale = 1.0f / drop->keep_prob;
-  a.drop_key.k0 = (uint32_t)(drop->seed & 0xFFFFFFFFull); a.drop_key.k1 = (uint32_t)(drop->seed >> 32);
-  a.drop_key.o0 = (uint32_t)(drop->offset & 0xFFFFFFFFull); a.drop_key.o1 = (uint32_t)(drop->offset >> 32);
-  a.drop_key.epoch = drop->epoch;
+  a.drop_key = make_key(drop->seed, drop->offset, drop->epoch);
   return STAG_OK;
 }
 static bool drop_on(const stag_gat_drop* drop) { return drop && drop->keep_prob < 1.0f; }
 
-// The global positions of a launch that draws (edge weights, or an attention-dropout mask): STAG_EINVAL outside what
-// the counter word names (counter_space_ok), STAG_ENOSYS across a 2^32 boundary (the kernels keep pos_hi fixed and
-// add the local position to pos_lo in 32 bits).
-static int check_positions(const stag_noise_spec* spec, int64_t n_edges, int32_t H, bool drawn) {
-  if (!drawn) return STAG_OK;
-  if (!counter_space_ok(spec->pos_base, n_edges, spec->chunk_base, ((int64_t)H + 3) / 4)) return STAG_EINVAL;
-  if (((uint64_t)spec->pos_base & 0xFFFFFFFFull) + (uint64_t)n_edges > (1ull << 32)) return STAG_ENOSYS;
-  return STAG_OK;
+// the forward's segment states: merged by the segment that arrives last, through a 32-bit buffer descriptor
+constexpr unsigned kGatFwdPlan = kPlanSegPtr | kPlanWorkspace | kPlanNarrow | kPlanCounters;
+
+// what every GAT argument block takes from the graph, the scores and the spec (the noise width is H)
+static void fill_gat_args(GatArgs& a, const stag_csr* csr, const float* el, const float* er, int32_t H, float neg_slope,
+                          const stag_noise_spec* spec, const float* norm_scale) {
+  a.indptr = csr->indptr; a.indices = csr->indices; a.eid = csr->eid; a.nidx = csr->nidx;
+  a.n_rows = csr->n_dst; a.el = el; a.er = er;
+  a.nscale = spec->in_norm ? norm_scale : nullptr;
+  a.H = H; a.neg_slope = neg_slope;
+  fill_spec(a, spec, 0);
 }
 
 extern "C" size_t stag_gat_workspace_bytes(int32_t n_seg, int32_t H, int32_t F) {
@@ -1952,7 +1952,7 @@ extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const fl
                             const float* er, const float* ft, int32_t H, int32_t F, float neg_slope,
                             const stag_noise_spec* spec, const float* norm_scale, const stag_gat_drop* drop,
                             float* out, float* stats_out, void* stream) {
-  if (!csr || !csr->indptr || csr->n_dst < 0 || csr->n_edges < 0) return STAG_EINVAL;
+  if (check_csr_header(csr)) return STAG_EINVAL;
   if (!spec || spec->kind < STAG_NOISE_NONE || spec->kind > STAG_NOISE_BERNOULLI) return STAG_EINVAL;
   if (!out || H <= 0 || F <= 0) return STAG_EINVAL;
   const int64_t HF64 = (int64_t)H * F;
@@ -1970,21 +1970,9 @@ extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const fl
   const int HF = (int)HF64;
 
   GatArgs a{};
-  a.indptr = csr->indptr; a.indices = csr->indices; a.eid = csr->eid; a.nidx = csr->nidx;
-  a.n_rows = csr->n_dst; a.el = el; a.er = er; a.ft = ft;
-  a.nscale = spec->in_norm ? norm_scale : nullptr;
-  a.H = H; a.F = F; a.HF = HF;
-  a.neg_slope = neg_slope; a.kind = spec->kind; a.p0 = spec->p0; a.p1 = spec->p1;
-  const bool logs = spec->kind == STAG_NOISE_NORMAL && spec->p1_log;
-  a.p0s = spec->p0_scalar; a.p1s = logs ? expf(spec->p1_scalar) : spec->p1_scalar;
-  a.pmode = spec->kind >= STAG_NOISE_NORMAL ? spec->param_mode : 0;
-  a.relu = (spec->relu ? kFlagRelu : 0) | (logs ? kFlagLogScale : 0);
   if (spec->deriv != 0) return STAG_EINVAL;
-  a.key.k0 = (uint32_t)(spec->seed & 0xFFFFFFFFull); a.key.k1 = (uint32_t)(spec->seed >> 32);
-  a.key.o0 = (uint32_t)(spec->offset & 0xFFFFFFFFull); a.key.o1 = (uint32_t)(spec->offset >> 32);
-  a.key.epoch = spec->epoch;
-  a.pos_lo = (uint32_t)((uint64_t)spec->pos_base & 0xFFFFFFFFull);
-  a.pos_hi = (uint32_t)((uint64_t)spec->pos_base >> 32);
+  fill_gat_args(a, csr, el, er, H, neg_slope, spec, norm_scale);
+  a.ft = ft; a.F = F; a.HF = HF;
   const int prc = check_positions(spec, csr->n_edges, H, spec->kind >= STAG_NOISE_NORMAL || drop_on(drop));
   if (prc) return prc;
   a.out = out; a.stats = stats_out;
@@ -1992,28 +1980,20 @@ extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const fl
   const uint64_t ftb = (uint64_t)csr->n_src * (uint64_t)HF * 4u;
   a.ft_bytes = (ftb < (1ull << 32) && csr->n_src < (1 << 24)) ? (uint32_t)ftb : 0u;
 
-  a.n_units = csr->n_dst;
-  const bool use_plan = plan && plan->n_units > 0;
-  if (use_plan) {
-    if (!plan->units || !aligned16(plan->units)) return STAG_EINVAL;
-    a.units = plan->units; a.n_units = plan->n_units;
-    if (plan->n_seg > 0) {
-      if (!plan->long_rows || !plan->long_seg_ptr || !plan->workspace || !plan->seg_counters)
-        return STAG_EINVAL;
-      const size_t need = stag_gat_workspace_bytes(plan->n_seg, H, F);
-      if (plan->workspace_bytes < need) return STAG_ENOMEM;
-      if (need >= (1ull << 32)) return STAG_ENOSYS;
-      a.long_rows = plan->long_rows; a.long_seg_ptr = plan->long_seg_ptr; a.n_long = plan->n_long;
-      a.seg_counters = plan->seg_counters; a.ws = plan->workspace;
-      a.ws_stride = (HF + 2 * H + 3) & ~3; a.ws_bytes = (uint32_t)need; a.n_seg = plan->n_seg;
-    }
+  const bool use_plan = plan_in_use(plan);
+  const size_t need = use_plan ? stag_gat_workspace_bytes(plan->n_seg, H, F) : 0;
+  const int plrc = check_plan(plan, kGatFwdPlan, need);
+  if (plrc) return plrc;
+  fill_plan(a, csr, plan);
+  if (use_plan && plan->n_seg > 0) {
+    a.seg_counters = plan->seg_counters; a.n_seg = plan->n_seg;
+    a.ws_stride = (HF + 2 * H + 3) & ~3; a.ws_bytes = (uint32_t)need;
   }
   bool vec = (F % 4 == 0) && aligned16(ft) && aligned16(out);
   if (a.ws) vec = vec && aligned16(a.ws) && (a.ws_stride % 4 == 0);
 
   int nchunk = (HF + 3) / 4;
-  int lpe = 4;
-  while (lpe < nchunk && lpe < 64) lpe <<= 1;
+  int lpe = lanes_for(nchunk, 4);
   int cpl = nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4);   // chunks of 4 channels per lane
   const int tpb = 256 / lpe;
   const dim3 grid((a.n_units + tpb - 1) / tpb);
@@ -2026,13 +2006,13 @@ extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const fl
                       lphp > 0 && lphp <= 64 && H * lphp <= 256;
   if (HF > 256 && !blk_ok) return STAG_ENOSYS;
   if (a.drop_keep > 0.f && !blk_ok) return STAG_ENOSYS;      // attention dropout lives in the cooperative kernels
+  if (check_csr(csr)) return STAG_EINVAL;
   if (blk_ok) {
     // workgroup-cooperative form: batches of units (stag_plan_blocks with STAG_BLOCK_EDGES / _UNITS)
     a.block_ptr = plan->block_ptr;
     a.lphp = lphp;
     nchunk = H * lphp;
-    lpe = 4;
-    while (lpe < nchunk && lpe < 64) lpe <<= 1;
+    lpe = lanes_for(nchunk, 4);
     cpl = nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4);
     a.hvec = aligned16(el) && aligned16(er) && (!a.nscale || aligned16(a.nscale));
     size_t lds_blk = (size_t)(kBlkEdges * H + 2 * kBlkUnits * H) * sizeof(float) +
@@ -2088,7 +2068,7 @@ extern "C" int stag_gat_fwd_mc(const stag_csr* csr, const stag_plan* plan, const
                                const float* ft, int32_t H, int32_t F, float neg_slope, const stag_noise_spec* spec,
                                int32_t n_samples, int64_t offset_stride, float* out, int64_t out_stride,
                                float* stats_out, int64_t stats_stride, void* stream) {
-  if (!csr || !csr->indptr || csr->n_dst < 0 || csr->n_edges < 0 || csr->n_src < 0) return STAG_EINVAL;
+  if (check_csr_header(csr) || csr->n_src < 0) return STAG_EINVAL;
   if (!spec || !out || !el || !er || !ft || (csr->n_edges > 0 && !csr->indices)) return STAG_EINVAL;
   if (H <= 0 || F <= 0 || n_samples < 1 || offset_stride < 0) return STAG_EINVAL;
   const int64_t HF64 = (int64_t)H * F;
@@ -2111,41 +2091,28 @@ extern "C" int stag_gat_fwd_mc(const stag_csr* csr, const stag_plan* plan, const
     return STAG_ENOSYS;
   const int HF = (int)HF64;
   const int nchunk = H * lphp;
-  int lpe = 4;
-  while (lpe < nchunk && lpe < 64) lpe <<= 1;
+  const int lpe = lanes_for(nchunk, 4);
   const int cpl = nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4);
   const int sp = cpl == 4 ? STAG_GAT_MC_SP_WIDE : STAG_GAT_MC_SP;
   const int wsp = n_samples < sp ? n_samples : sp;
 
   GatMcArgs g{};
   GatArgs& a = g.a;
-  a.indptr = csr->indptr; a.indices = csr->indices; a.eid = csr->eid; a.nidx = csr->nidx;
-  a.n_rows = csr->n_dst; a.el = el; a.er = er; a.ft = ft;
-  a.H = H; a.F = F; a.HF = HF;
-  a.neg_slope = neg_slope; a.kind = spec->kind; a.p0 = spec->p0; a.p1 = spec->p1;
-  const bool logs = spec->kind == STAG_NOISE_NORMAL && spec->p1_log;
-  a.p0s = spec->p0_scalar; a.p1s = logs ? expf(spec->p1_scalar) : spec->p1_scalar;
-  a.pmode = spec->param_mode;
-  a.relu = (spec->relu ? kFlagRelu : 0) | (logs ? kFlagLogScale : 0);
-  a.key.k0 = (uint32_t)(spec->seed & 0xFFFFFFFFull); a.key.k1 = (uint32_t)(spec->seed >> 32);
-  a.key.epoch = spec->epoch;
-  a.pos_lo = (uint32_t)((uint64_t)spec->pos_base & 0xFFFFFFFFull);
-  a.pos_hi = (uint32_t)((uint64_t)spec->pos_base >> 32);
+  fill_gat_args(a, csr, el, er, H, neg_slope, spec, nullptr);   // (every pass sets its own offset in the key)
+  a.ft = ft; a.F = F; a.HF = HF;
   const uint64_t ftb = (uint64_t)csr->n_src * (uint64_t)HF * 4u;
   a.ft_bytes = (ftb < (1ull << 32) && csr->n_src < (1 << 24)) ? (uint32_t)ftb : 0u;
-  a.units = plan->units; a.n_units = plan->n_units;
+  fill_plan(a, csr, plan);
   a.ws_stride = (HF + 2 * H + 3) & ~3;
+  const size_t need = stag_gat_workspace_bytes(plan->n_seg, H, F) * (size_t)wsp;
+  const int plrc = check_plan_segments(plan, kGatFwdPlan, need);
+  if (plrc) return plrc;
   if (plan->n_seg > 0) {
-    if (!plan->long_rows || !plan->long_seg_ptr || !plan->workspace || !plan->seg_counters) return STAG_EINVAL;
-    const size_t need = stag_gat_workspace_bytes(plan->n_seg, H, F) * (size_t)wsp;
-    if (plan->workspace_bytes < need) return STAG_ENOMEM;
-    if (need >= (1ull << 32)) return STAG_ENOSYS;     // segment states go through a 32-bit buffer descriptor
     if (!aligned16(plan->workspace)) return STAG_ENOSYS;
-    a.long_rows = plan->long_rows; a.long_seg_ptr = plan->long_seg_ptr; a.n_long = plan->n_long;
-    a.seg_counters = plan->seg_counters; a.ws = plan->workspace;
-    a.ws_bytes = (uint32_t)need; a.n_seg = plan->n_seg;
+    a.seg_counters = plan->seg_counters; a.ws_bytes = (uint32_t)need; a.n_seg = plan->n_seg;
   }
   if (csr->n_dst == 0) return STAG_OK;
+  if (check_csr(csr)) return STAG_EINVAL;
   a.block_ptr = plan->block_ptr;
   a.lphp = lphp;
   a.hvec = aligned16(el) && aligned16(er);
@@ -2158,7 +2125,7 @@ extern "C" int stag_gat_fwd_mc(const stag_csr* csr, const stag_plan* plan, const
   for (int32_t s0 = 0; s0 < n_samples; s0 += sp) {
     g.ns = (n_samples - s0 < sp) ? n_samples - s0 : sp;
     const uint64_t off = spec->offset + (uint64_t)s0 * (uint64_t)offset_stride;
-    a.key.o0 = (uint32_t)(off & 0xFFFFFFFFull); a.key.o1 = (uint32_t)(off >> 32);
+    a.key = make_key(spec->seed, off, spec->epoch);
     a.out = out + (int64_t)s0 * out_stride;
     a.stats = stats_out ? stats_out + (int64_t)s0 * stats_stride : nullptr;
     size_t lds = (size_t)g.ns * (kBlkEdges * H + 2 * kBlkUnits * H) * sizeof(float) +
@@ -2189,38 +2156,19 @@ extern "C" int stag_gat_fwd_mc(const stag_csr* csr, const stag_plan* plan, const
 static int fill_edge_args(GatArgs& a, const stag_csr* csr, const stag_plan* plan, const float* el,
                           const float* er, int32_t H, float neg_slope, const stag_noise_spec* spec,
                           const float* norm_scale, const float* stats) {
-  a.indptr = csr->indptr; a.indices = csr->indices; a.eid = csr->eid; a.nidx = csr->nidx;
-  a.n_rows = csr->n_dst; a.el = el; a.er = er;
-  a.nscale = spec->in_norm ? norm_scale : nullptr;
-  a.H = H; a.neg_slope = neg_slope;
-  const bool logs = spec->kind == STAG_NOISE_NORMAL && spec->p1_log;
-  a.kind = spec->kind; a.p0 = spec->p0; a.p1 = spec->p1; a.p0s = spec->p0_scalar;
-  a.p1s = logs ? expf(spec->p1_scalar) : spec->p1_scalar;
-  a.pmode = spec->kind >= STAG_NOISE_NORMAL ? spec->param_mode : 0;
-  a.relu = (spec->relu ? kFlagRelu : 0) | (logs ? kFlagLogScale : 0);
-  a.key.k0 = (uint32_t)(spec->seed & 0xFFFFFFFFull); a.key.k1 = (uint32_t)(spec->seed >> 32);
-  a.key.o0 = (uint32_t)(spec->offset & 0xFFFFFFFFull); a.key.o1 = (uint32_t)(spec->offset >> 32);
-  a.key.epoch = spec->epoch;
-  a.pos_lo = (uint32_t)((uint64_t)spec->pos_base & 0xFFFFFFFFull);
-  a.pos_hi = (uint32_t)((uint64_t)spec->pos_base >> 32);
+  fill_gat_args(a, csr, el, er, H, neg_slope, spec, norm_scale);
   // (a caller with attention dropout checks the positions itself, before it launches anything)
   const int prc = check_positions(spec, csr->n_edges, H, spec->kind >= STAG_NOISE_NORMAL);
   if (prc) return prc;
   a.stats = const_cast<float*>(stats);
-  a.n_units = csr->n_dst;
-  if (plan && plan->n_units > 0) {
-    if (!plan->units || !aligned16(plan->units)) return STAG_EINVAL;
-    if (plan->n_seg > 0 && !plan->long_rows) return STAG_EINVAL;
-    a.units = plan->units; a.n_units = plan->n_units; a.long_rows = plan->long_rows;
-  }
-  return STAG_OK;
+  return fill_units(a, csr, plan);
 }
 
 extern "C" int stag_gat_attn(const stag_csr* csr, const stag_plan* plan, const float* el,
                              const float* er, int32_t H, float neg_slope, const stag_noise_spec* spec,
                              const float* norm_scale, const float* stats, float* attn_out,
                              void* stream) {
-  if (!csr || !csr->indptr || csr->n_dst < 0 || csr->n_edges < 0) return STAG_EINVAL;
+  if (check_csr_header(csr)) return STAG_EINVAL;
   if (!spec || spec->kind < STAG_NOISE_NONE || spec->kind > STAG_NOISE_BERNOULLI || spec->deriv) return STAG_EINVAL;
   if (!attn_out || !stats || H <= 0 || H > 64) return STAG_EINVAL;
   if (spec->chunk_base != 0) return STAG_ENOSYS;
@@ -2231,6 +2179,7 @@ extern "C" int stag_gat_attn(const stag_csr* csr, const stag_plan* plan, const f
   GatArgs a{};
   const int rc = fill_edge_args(a, csr, plan, el, er, H, neg_slope, spec, norm_scale, stats);
   if (rc) return rc;
+  if (check_csr(csr)) return STAG_EINVAL;
   a.attn = attn_out;
   hipLaunchKernelGGL(gat_attn_kernel, dim3((a.n_units + 31) / 32), dim3(256), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
@@ -2241,7 +2190,7 @@ extern "C" int stag_gat_bwd_edge(const stag_csr* csr, const stag_plan* plan, con
                                  const float* out, int32_t H, int32_t F, float neg_slope,
                                  const stag_noise_spec* spec, const float* norm_scale, float* de,
                                  float* dw, float* attn_out, void* stream) {
-  if (!csr || !csr->indptr || csr->n_dst < 0 || csr->n_edges < 0) return STAG_EINVAL;
+  if (check_csr_header(csr)) return STAG_EINVAL;
   if (!spec || spec->kind < STAG_NOISE_NONE || spec->kind > STAG_NOISE_BERNOULLI || spec->deriv) return STAG_EINVAL;
   if (!de || H <= 0 || F <= 0) return STAG_EINVAL;
   const int64_t HF64 = (int64_t)H * F;
@@ -2258,11 +2207,10 @@ extern "C" int stag_gat_bwd_edge(const stag_csr* csr, const stag_plan* plan, con
   GatArgs& a = ba.f;
   const int rc = fill_edge_args(a, csr, plan, el, er, H, neg_slope, spec, norm_scale, stats);
   if (rc) return rc;
+  if (check_csr(csr)) return STAG_EINVAL;
   a.ft = ft; a.F = F; a.HF = HF; a.attn = attn_out;
   ba.g = g; ba.gdo = nullptr; ba.out = out; ba.de = de; ba.dw = dw;
-  const int nchunk = (HF + 3) / 4;
-  int lpe = 4;
-  while (lpe < nchunk) lpe <<= 1;
+  const int lpe = lanes_for((HF + 3) / 4, 4);   // (H * F <= 256: at most a wave)
   const int tpb = 256 / lpe;
   const dim3 grid((a.n_units + tpb - 1) / tpb);
   const size_t lds_bytes = (size_t)3 * 256 * H * sizeof(float);
@@ -2293,7 +2241,7 @@ extern "C" int stag_gat_bwd_two_pass(const stag_csr* csr, const stag_plan* plan,
                                      const stag_gat_drop* drop, float* d_el, float* d_er, float* d_ft, float* dw,
                                      float* ade_ws, void* stream) {
   if (drop_on(drop)) return STAG_ENOSYS;               // attention dropout: stag_gat_bwd
-  if (!csr || !csr_t || !csr->indptr || !csr_t->indptr || csr->n_dst < 0 || csr->n_edges < 0) return STAG_EINVAL;
+  if (check_csr_header(csr) || !csr_t || !csr_t->indptr) return STAG_EINVAL;
   if (csr_t->n_edges != csr->n_edges || csr_t->n_dst != csr->n_src || csr_t->n_src != csr->n_dst) return STAG_EINVAL;
   if (!spec || spec->kind < STAG_NOISE_NONE || spec->kind > STAG_NOISE_BERNOULLI || spec->deriv) return STAG_EINVAL;
   if (!d_el || !d_er || !d_ft || !ade_ws || H <= 0 || F <= 0) return STAG_EINVAL;
@@ -2320,6 +2268,9 @@ extern "C" int stag_gat_bwd_two_pass(const stag_csr* csr, const stag_plan* plan,
   GatArgs& a = ba.f;
   int rc = fill_edge_args(a, csr, plan, el, er, H, neg_slope, spec, norm_scale, stats);
   if (rc) return rc;
+  // the source pass's plan too, before the edge pass is enqueued
+  if (check_plan_units(plan_t, 0) || check_plan_segments(plan_t, kPlanSegPtr)) return STAG_EINVAL;
+  if (check_csr(csr) || check_csr(csr_t)) return STAG_EINVAL;
   a.ft = ft; a.F = F; a.HF = HF; a.lphp = lph;
   const uint64_t ftb = (uint64_t)csr->n_src * (uint64_t)HF * 4u;
   a.ft_bytes = (ftb < (1ull << 32) && csr->n_src < (1 << 24)) ? (uint32_t)ftb : 0u;
@@ -2327,8 +2278,7 @@ extern "C" int stag_gat_bwd_two_pass(const stag_csr* csr, const stag_plan* plan,
   a.hvec = aligned16(el) && aligned16(er) && aligned16(stats) && (!a.nscale || aligned16(a.nscale));
   ba.g = g; ba.out = out; ba.ade = ade_ws; ba.d_er = d_er; ba.dw = dw; ba.ws = plan->workspace;
   const int nchunk = (HF + 3) / 4;
-  int lpe = 4;
-  while (lpe < nchunk && lpe < 64) lpe <<= 1;
+  const int lpe = lanes_for(nchunk, 4);
   const int cpl = nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4);
   size_t lds_e = (size_t)kBlkEdges * H * (dw ? 3 : 2) * sizeof(float) +
                  (size_t)(kBlkEdges + kBlkUnits + 4) * sizeof(int) + (size_t)kBlkUnits * sizeof(int4);
@@ -2356,8 +2306,6 @@ extern "C" int stag_gat_bwd_two_pass(const stag_csr* csr, const stag_plan* plan,
   const uint64_t gb = (uint64_t)csr->n_dst * (uint64_t)HF * 4u;
   sa.g_bytes = (gb < (1ull << 32) && csr->n_dst < (1 << 24)) ? (uint32_t)gb : 0u;
   sa.d_ft = d_ft; sa.d_el = d_el; sa.ws = plan->workspace;   // the edge pass's partials are consumed by now (stream order)
-  if (!plan_t->units || !aligned16(plan_t->units)) return STAG_EINVAL;
-  if (plan_t->n_seg > 0 && (!plan_t->long_rows || !plan_t->long_seg_ptr)) return STAG_EINVAL;
   size_t lds_s = (size_t)kBlkEdges * H * 2 * sizeof(float) + (size_t)(kBlkEdges + kBlkUnits + 4) * sizeof(int) +
                  (size_t)kBlkUnits * sizeof(int4);
   if (lds_s < STAG_GAT_LDS_MIN_BWD) lds_s = STAG_GAT_LDS_MIN_BWD;
@@ -2452,7 +2400,7 @@ static int gat_bwd_impl(const stag_csr* csr, const stag_plan* plan, const stag_c
                         float neg_slope, const stag_noise_spec* spec, const float* norm_scale,
                         const stag_gat_drop* drop, float* d_el, float* d_er, float* d_ft, float* dw,
                         float* scratch, void* stream, float* dp0, float* dp1, float* dp_ws, int stages) {
-  if (!csr || !csr_t || !csr->indptr || !csr_t->indptr || csr->n_dst < 0 || csr->n_edges < 0) return STAG_EINVAL;
+  if (check_csr_header(csr) || !csr_t || !csr_t->indptr) return STAG_EINVAL;
   if (csr_t->n_edges != csr->n_edges || csr_t->n_dst != csr->n_src || csr_t->n_src != csr->n_dst) return STAG_EINVAL;
   if (!spec || spec->kind < STAG_NOISE_NONE || spec->kind > STAG_NOISE_BERNOULLI || spec->deriv) return STAG_EINVAL;
   if (!d_el || !d_er || !d_ft || !scratch || H <= 0 || F <= 0) return STAG_EINVAL;
@@ -2471,11 +2419,9 @@ static int gat_bwd_impl(const stag_csr* csr, const stag_plan* plan, const stag_c
   if (spec->kind == STAG_NOISE_EXPLICIT && !spec->p0 && csr->n_edges > 0) return STAG_EINVAL;
   const int prc = check_positions(spec, csr->n_edges, H, spec->kind >= STAG_NOISE_NORMAL || drop_on(drop));
   if (prc) return prc;
-  if (!plan_t->units || !aligned16(plan_t->units)) return STAG_EINVAL;
-  if (plan_t->n_seg > 0 && (!plan_t->long_rows || !plan_t->long_seg_ptr)) return STAG_EINVAL;
-  const bool fplan = plan && plan->n_units > 0;
-  if (fplan && (!plan->units || !aligned16(plan->units))) return STAG_EINVAL;
-  if (fplan && plan->n_seg > 0 && (!plan->long_rows || !plan->long_seg_ptr)) return STAG_EINVAL;
+  if (check_plan_units(plan_t, 0) || check_plan_segments(plan_t, kPlanSegPtr)) return STAG_EINVAL;
+  const bool fplan = plan_in_use(plan);
+  if (check_plan(plan, kPlanSegPtr)) return STAG_EINVAL;
   const int HF = (int)HF64;
   const size_t need = stag_gat_bwd_workspace_bytes(fplan ? plan->n_seg : 0, plan_t->n_seg, H, F);
   // segment partials of BOTH orientations live in the forward plan's workspace, one after the other
@@ -2485,9 +2431,18 @@ static int gat_bwd_impl(const stag_csr* csr, const stag_plan* plan, const stag_c
   float* pack = scratch + (size_t)csr->n_edges * H;        // 16-byte aligned whenever H % 4 == 0 (the vector form)
 
   const int nchunk = H * lphp;                          // lanes a row takes
-  int lpe = 4;
-  while (lpe < nchunk && lpe < 64) lpe <<= 1;
+  const int lpe = lanes_for(nchunk, 4);
   const int cpl = nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4);
+
+  // the source pass's arguments: its refusals come before the first launch too
+  GatBwd1Args ba{};
+  GatArgs& a = ba.f;
+  if (stages & STAG_GAT_BWD_SOURCE) {
+    const int rc = fill_edge_args(a, csr_t, plan_t, el, er, H, neg_slope, spec, norm_scale, stats);
+    if (rc) return rc;
+    if (fill_drop(a, drop)) return STAG_EINVAL;
+  }
+  if (check_csr(csr) || check_csr(csr_t)) return STAG_EINVAL;
 
   // 1. sdot[v,h] = <G[v,h,:], out[v,h,:]>
   if (stages & STAG_GAT_BWD_ROWDOT) {
@@ -2505,13 +2460,8 @@ static int gat_bwd_impl(const stag_csr* csr, const stag_plan* plan, const stag_c
 
   // 2. the source-major pass
   if (stages & STAG_GAT_BWD_SOURCE) {
-  GatBwd1Args ba{};
-  GatArgs& a = ba.f;
-  int rc = fill_edge_args(a, csr_t, plan_t, el, er, H, neg_slope, spec, norm_scale, stats);
-  if (rc) return rc;
   a.ft = ft; a.F = F; a.HF = HF; a.lphp = lphp;
   a.block_ptr = plan_t->block_ptr;
-  if (fill_drop(a, drop)) return STAG_EINVAL;
   a.hvec = aligned16(el) && aligned16(pack) && (!a.nscale || aligned16(a.nscale));
   ba.g = g; ba.pack = pack; ba.d_ft = d_ft; ba.d_el = d_el; ba.dsl = dsl; ba.dw = dw;
   ba.dp_part = dp_ws;
