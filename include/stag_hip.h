@@ -611,6 +611,22 @@ int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const float* el, co
                  const stag_noise_spec* spec, const float* norm_scale, const stag_gat_drop* drop,
                  float* out, float* stats_out, void* stream);
 
+/* stag_gat_fwd on fp16 / bf16 feature rows, gathered as they are: ft is [N, H*F] of ft_dtype (STAG_DTYPE_F16 |
+ * STAG_DTYPE_BF16), packed rows; a lane loads 8 bytes of a row instead of 16 and widens them in registers (exact).
+ * el, er, norm_scale, out, stats_out are fp32 exactly as for stag_gat_fwd, and so are the segment states: the same
+ * plan and the same workspace, stag_gat_workspace_bytes().  The draws, the softmax and the order of every sum are
+ * stag_gat_fwd's, so out and stats_out are bit-identical to stag_gat_fwd on the widened rows, for every kind, parameter
+ * mode, relu, p1_log, in-norm, attention dropout, nidx, pos_base and epoch that entry takes.
+ * Workgroup-cooperative form only.  STAG_EINVAL: what stag_gat_fwd refuses, and an unknown ft_dtype.  STAG_ENOSYS (the
+ * caller widens ft and calls stag_gat_fwd): no block plan (stag_plan.block_ptr), F % 4 != 0, H > 16, H * lanes_per_head
+ * > 256, plan->seg_len > STAG_BLOCK_EDGES, ft not 8-byte aligned, out or the workspace not 16-byte aligned,
+ * spec.chunk_base != 0, a launch across a 2^32 position boundary.  STAG_ENOMEM: the workspace is too small.  Every
+ * argument is checked before any device work.                                                                      */
+int stag_gat_fwd_half(const stag_csr* csr, const stag_plan* plan, const float* el, const float* er,
+                      const void* ft, int32_t ft_dtype, int32_t H, int32_t F, float neg_slope,
+                      const stag_noise_spec* spec, const float* norm_scale, const stag_gat_drop* drop,
+                      float* out, float* stats_out, void* stream);
+
 /* n_samples Monte-Carlo draws of stag_gat_fwd from ONE gather of the ft rows per pass (the reference's Monte-Carlo
  * loop, stag/models.py:45-55, on a first GAT layer: the rows are the same for every sample, only the H-wide draws
  * differ).  Sample s is stag_gat_fwd with spec.offset + s * offset_stride (mod 2^64, plus *spec.epoch as usual), bit

@@ -172,6 +172,8 @@ def bind(path):
     l.stag_gat_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     l.stag_gat_fwd.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, _vp, _vp, C.c_int32, C.c_int32,
                                C.c_float, C.POINTER(NoiseSpec), _vp, C.POINTER(GatDrop), _vp, _vp, _vp]
+    l.stag_gat_fwd_half.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_float, C.POINTER(NoiseSpec), _vp, C.POINTER(GatDrop), _vp, _vp, _vp]
     l.stag_gat_fwd_mc_workspace_bytes.restype = C.c_size_t
     l.stag_gat_fwd_mc_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     l.stag_gat_fwd_mc.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_float,

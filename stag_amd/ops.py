@@ -1503,13 +1503,74 @@ def attn_drop_fusable(H, F, seg_len, want_attn=False):
     return not want_attn and _GAT_BWD_FUSED and _GAT_BWD_ONE_GATHER and gat_cooperative_shape(H, F, seg_len)
 
 
+# stag_gat_fwd_half on fp16 / bf16 ft rows | ft.float() + stag_gat_fwd.  The two routes give the same bits, so the switch
+# is a speed decision only.  True because, at cfg5 (8 x 32, bf16 rows, us per call, profiles/r10/gat_half_rows.txt), the
+# half launch is not slower than the cast route for any kind timed — none 147.8 against 264.6, Normal 149.5 / 266.2,
+# Normal + attention dropout 153.6 / 268.9; two repeats of the cast route differ by 0.0-0.5.  
+GAT_HALF_ROWS = True
+# zoo.GAT under CUDA autocast with a half dtype: ft from a half GEMM (and el / er from the input through the folded
+# attention weight, in fp32) | everything in fp32 as ops.node_linear pins it.  Off: a layer under autocast computes
+# what it always did.
+GAT_HALF_FT = False
+
+
+def gat_half_rows_why_not(ft, seg_len=DEFAULT_SEG_LEN, graph=None, noise=None, attn_fn=None, ignore_switch=False):
+    """The first reason ops.gat_aggregate keeps the cast route (ft.float(), stag_gat_fwd) for this call, or None: the
+    forward launches stag_gat_fwd_half on ft as it is.  One clause per refusal of the entry point (include/stag_hip.h)
+    and per path that has no half form (the composed path, Monte-Carlo batches, shards, a traced graph).
+    ignore_switch: whatever GAT_HALF_ROWS says (zoo.GAT asks whether a half ft COULD be gathered as it is: the two
+    routes give the same bits, so what the layer computes must not depend on the switch)."""
+    if not GAT_HALF_ROWS and not ignore_switch:
+        return "switch"
+    if ft.dtype not in _HALF_DTYPES:
+        return "dtype"
+    if ft.dim() != 3 or not gat_cooperative_shape(ft.shape[1], ft.shape[2], seg_len):
+        return "shape"
+    if attn_fn is not None:
+        return "attention function"
+    if noise is not None and getattr(noise, "n_samples", 1) != 1:
+        return "monte-carlo"
+    if getattr(graph, "is_shard", False) or (noise is not None and getattr(getattr(noise, "graph", None), "is_shard", False)):
+        return "shard"
+    if torch.compiler.is_compiling():
+        return "compiling"
+    if not ft.is_contiguous():
+        return "strides"
+    if not ft.is_cuda:
+        return "device"
+    if ft.data_ptr() % 8 != 0:
+        return "alignment"
+    return None
+
+
+def gat_half_rows_ok(ft, seg_len=DEFAULT_SEG_LEN, graph=None, noise=None, attn_fn=None):
+    return gat_half_rows_why_not(ft, seg_len, graph, noise, attn_fn) is None
+
+
+def _gat_fwd_half_raw(csrv, plan_t, el, er, ft, H, F, neg_slope, spec, nscale, drop, out, stats, seg_len, dev):
+    """One stag_gat_fwd_half launch: ft [n_src, H, F] fp16 | bf16 as it is, out / stats fp32.  Bound through ctypes only;
+    returns the plan struct (stag_gat_attn takes the same one)."""
+    nbytes = _lib.lib().stag_gat_workspace_bytes(plan_t["n_seg"], H, F)
+    plan_c, _keep = _plan_struct(csrv, seg_len, 1, nbytes, dev, plan_t=plan_t, gat_width=H * F)
+    cs = csrv.struct()
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_gat_fwd_half(C.byref(cs), C.byref(plan_c), _lib.ptr(el), _lib.ptr(er), _lib.ptr(ft),
+                                          _HALF_DTYPES[ft.dtype], H, F, float(neg_slope), C.byref(spec), _lib.ptr(nscale),
+                                          C.byref(drop) if drop is not None else None,
+                                          _lib.ptr(out), _lib.ptr(stats), _lib.stream_of(dev))
+    _lib.check(rc, "stag_gat_fwd_half")
+    return plan_c, _keep
+
+
 class _GatAggregate(torch.autograd.Function):
     """p0, p1 (optional): the live parameter tensors of a reparameterised `noise` (vi=True): the draw stays in the
     kernels, forward and backward, and the backward returns their finished gradients (stag_gat_bwd_dp)."""
 
     @staticmethod
     def forward(ctx, el, er, ft, w, graph, noise, neg_slope, want_attn, seg_len, attn_drop=None, p0=None, p1=None):
-        el, er, ft = _f32c(el), _f32c(er), _f32c(ft)
+        # half rows (ops.GAT_HALF_ROWS): the forward gathers ft as it is, and the half ft is what is kept for the backward
+        half = gat_half_rows_ok(ft, seg_len, graph, noise)
+        el, er, ft = _f32c(el), _f32c(er), (ft if half else _f32c(ft))
         ctx.pshapes = None if p0 is None else (p0.shape, p1.shape)
         H, F = ft.shape[1], ft.shape[2]
         csrv = graph.csr
@@ -1531,7 +1592,7 @@ class _GatAggregate(torch.autograd.Function):
         stats = (torch.empty((csrv.n_dst, 2 * H), dtype=torch.float32, device=dev)
                  if (want_attn or need_grad) else None)
         plan_t = csrv.plan(seg_len, need=True)       # the cooperative kernels want the plan's unit batches
-        if _torch_ext.available() and not want_attn and plan_t is not None:
+        if _torch_ext.available() and not want_attn and plan_t is not None and not half:
             # the dispatcher op (csrc/torch_ext.cpp: stag::gat_fwd): same library call, visible to a compiled graph
             targs = noise.torch_args() if noise is not None else (_explicit_spec(w) if w is not None else _NONE_ARGS)
             if attn_drop is not None and noise is None:
@@ -1543,18 +1604,23 @@ class _GatAggregate(torch.autograd.Function):
                 ctx.attn_drop = attn_drop
                 ctx.save_for_backward(el, er, ft, w, stats_t, out, nscale)
             return out
-        nbytes = _lib.lib().stag_gat_workspace_bytes(plan_t["n_seg"], H, F) if plan_t is not None else 0
-        plan_c, _keep = _plan_struct(csrv, seg_len, 1, nbytes, dev, plan_t=plan_t, gat_width=H * F)
         cs = csrv.struct()
         attn = None
         drop = _gat_drop_struct(attn_drop)
+        if half:
+            plan_c, _keep = _gat_fwd_half_raw(csrv, plan_t, el, er, ft, H, F, neg_slope, spec, nscale, drop, out, stats,
+                                              seg_len, dev)
+        else:
+            nbytes = _lib.lib().stag_gat_workspace_bytes(plan_t["n_seg"], H, F) if plan_t is not None else 0
+            plan_c, _keep = _plan_struct(csrv, seg_len, 1, nbytes, dev, plan_t=plan_t, gat_width=H * F)
         with _lib.on_device(dev):
-            rc = _lib.lib().stag_gat_fwd(C.byref(cs), C.byref(plan_c) if plan_c is not None else None,
-                                         _lib.ptr(el), _lib.ptr(er), _lib.ptr(ft), H, F,
-                                         float(neg_slope), C.byref(spec), _lib.ptr(nscale),
-                                         C.byref(drop) if drop is not None else None,
-                                         _lib.ptr(out), _lib.ptr(stats), _lib.stream_of(dev))
-            _lib.check(rc, "stag_gat_fwd")
+            if not half:
+                rc = _lib.lib().stag_gat_fwd(C.byref(cs), C.byref(plan_c) if plan_c is not None else None,
+                                             _lib.ptr(el), _lib.ptr(er), _lib.ptr(ft), H, F,
+                                             float(neg_slope), C.byref(spec), _lib.ptr(nscale),
+                                             C.byref(drop) if drop is not None else None,
+                                             _lib.ptr(out), _lib.ptr(stats), _lib.stream_of(dev))
+                _lib.check(rc, "stag_gat_fwd")
             if want_attn:
                 attn = torch.empty((csrv.n_edges, H), dtype=torch.float32, device=dev)
                 rc = _lib.lib().stag_gat_attn(C.byref(cs), C.byref(plan_c) if plan_c is not None else None,
@@ -1575,6 +1641,7 @@ class _GatAggregate(torch.autograd.Function):
     def backward(ctx, grad_out, *unused):
         el, er, ft, w, stats, out, nscale = ctx.saved_tensors
         graph, noise = ctx.graph, ctx.noise
+        ft = _f32c(ft)      # (a half ft of the half-row forward: widened for the length of this call; d ft leaves as fp32)
         H, F = ft.shape[1], ft.shape[2]
         HF = H * F
         csrv, csrt = graph.csr, graph.csr_t
@@ -1945,6 +2012,8 @@ def gat_aggregate_mc(graph, el, er, ft, neg_slope, noise, n_samples, offset_stri
     if not fused:
         if n_samples == 1:
             return one(0).unsqueeze(0)
+        if ft.dtype in _HALF_DTYPES:
+            ft = ft.float()        # a Monte-Carlo batch keeps the cast route (gat_half_rows_why_not): widened once for the loop
         return torch.stack([one(s) for s in range(n_samples)], 0)
     if needs_grad:
         return _GatAggregateMC.apply(el, er, ft, graph, noise, int(n_samples), int(offset_stride), float(neg_slope),

@@ -68,6 +68,23 @@ class GAT(torch.nn.Module):
         Fp = (F + 3) // 4 * 4
         return Fp if ops.gat_cooperative_shape(H, Fp, ops.DEFAULT_SEG_LEN) else F
 
+    def _half_ft(self, graph, h, H, F, edge_weight, get_attention):
+        """ops.GAT_HALF_FT is on, CUDA autocast is on with a half dtype, and ops.gat_aggregate could launch
+        stag_gat_fwd_half on a [N, H, F] ft of that dtype (F: the padded head width; ops.GAT_HALF_ROWS aside: it picks
+        between two routes of the same bits, so the layer's result does not depend on it)."""
+        if not (ops.GAT_HALF_FT and h.is_cuda and torch.is_autocast_enabled()):
+            return False
+        dtype = torch.get_autocast_dtype("cuda")
+        if dtype not in (torch.float16, torch.bfloat16):
+            return False
+        # attention dropout outside the fused kernels is a function of a[E, H] on the composed path: no half form
+        composed_drop = (self.training and self.attn_drop.p > 0.0
+                         and not ops.attn_drop_fusable(H, F, ops.DEFAULT_SEG_LEN, get_attention))
+        probe = torch.empty((0, H, F), dtype=dtype, device=h.device)
+        noise = edge_weight if isinstance(edge_weight, ops.EdgeNoise) else None
+        return ops.gat_half_rows_why_not(probe, ops.DEFAULT_SEG_LEN, graph, noise, attn_fn=True if composed_drop else None,
+                                         ignore_switch=True) is None
+
     def forward(self, graph, feat, get_attention=False, edge_weight=None):
         H, F = self._num_heads, self._out_feats
         n_mc = edge_weight.n_samples if isinstance(edge_weight, ops.EdgeNoise) else 1
@@ -90,12 +107,24 @@ class GAT(torch.nn.Module):
             F_out, F = F, Fp
         else:
             wp, attn_l, attn_r, F_out = self.fc.weight, self.attn_l, self.attn_r, F
-        ft = ops.node_linear(h, wp.t()).view(-1, H, F)
-        # el[n,h] = sum_f ft[n,h,f] attn_l[h,f], er likewise (zoo/gat.py:109-110).  The elementwise-multiply +
-        # reduce form costs 2 x 242 us at cfg5 (and as much again in the backward); ops.head_dot is one pass
-        # over ft forward and one back.  Head widths it does not take go through ONE [N, HF] x [HF, 2H]
-        # product with a block-diagonal right side.
-        lr = ops.head_dot(ft, attn_l, attn_r)
+        if self._half_ft(graph, h, H, F, edge_weight, get_attention):
+            # ops.GAT_HALF_FT under autocast: ft comes out of a half GEMM (torch's own autograd) and is gathered as it is
+            # (stag_gat_fwd_half).  el / er take no pass over ft: el[n,h] = sum_f (h_n . wp[hF+f]) attn_l[h,f] =
+            # h_n . (sum_f attn_l[h,f] wp[hF+f]) — the attention vectors folded into the weight, a parameter-sized
+            # product, then one fp32 [N, in] x [in, 2H] GEMM: more accurate than a dot over the rounded ft, and
+            # ops.head_dot's forward and backward passes over ft are gone.
+            ft = torch.nn.functional.linear(h, wp).view(-1, H, F)
+            w3 = wp.float().reshape(H, F, -1)
+            w_lr = torch.cat([(w3 * attn_l.float().reshape(H, F, 1)).sum(1), (w3 * attn_r.float().reshape(H, F, 1)).sum(1)], 0)
+            elr = ops.node_linear(h, w_lr.t())
+            lr = (elr[:, :H], elr[:, H:])
+        else:
+            ft = ops.node_linear(h, wp.t()).view(-1, H, F)
+            # el[n,h] = sum_f ft[n,h,f] attn_l[h,f], er likewise (zoo/gat.py:109-110).  The elementwise-multiply +
+            # reduce form costs 2 x 242 us at cfg5 (and as much again in the backward); ops.head_dot is one pass
+            # over ft forward and one back.  Head widths it does not take go through ONE [N, HF] x [HF, 2H]
+            # product with a block-diagonal right side.
+            lr = ops.head_dot(ft, attn_l, attn_r)
         if lr is not None:
             el, er = lr
         else:

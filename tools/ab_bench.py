@@ -40,6 +40,8 @@ def run(argv):
     ap.add_argument("--seg-len", type=int, default=64)
     ap.add_argument("--mc", type=int, default=0, help="time ops.aggregate_mc with this many Monte-Carlo samples per call")
     ap.add_argument("--per-edge", action="store_true", help="Normal noise with [E, 1] parameters (an AmortizedDistribution's heads)")
+    ap.add_argument("--gat-half", default=None, choices=["bf16", "fp16"],
+                    help="time ops.gat_aggregate on an 8 x 32 ft of this dtype (stag_gat_fwd_half; --noise none | normal)")
     ap.add_argument("--graph", default="arxiv", choices=["arxiv", "ppi"],
                     help="ppi: the 24-graph PPI-sized batch (BASELINE configs[2]) with the XCD-aware order on, mean reducer")
     args = ap.parse_args(argv)
@@ -67,7 +69,16 @@ def run(argv):
         handles[os.path.basename(path)[len("libstag_"):-3]] = l
     times = {k: [] for k in handles}
     ref = None
-    if args.per_edge:
+    if args.gat_half:
+        H, F = 8, 32
+        el, er = torch.randn(n, H, device=dev), torch.randn(n, H, device=dev)
+        ft = torch.randn(n, H, F, device=dev).to(torch.bfloat16 if args.gat_half == "bf16" else torch.float16)
+        ops.GAT_HALF_ROWS = True
+        nz = lambda i: None if args.noise == "none" else stag_amd.EdgeNoise(g, H, _lib.NOISE_NORMAL, 1.0, 0.5, seed=5, offset=i)
+        with torch.no_grad():
+            assert torch.equal(ops.gat_aggregate(g, el, er, ft, 0.2, nz(0)), ops.gat_aggregate(g, el, er, ft.float(), 0.2, nz(0)))
+        one = lambda i: ops.gat_aggregate(g, el, er, ft, 0.2, nz(i), seg_len=args.seg_len)
+    elif args.per_edge:
         E = g.number_of_edges()
         loc = torch.rand(E, 1, device=dev) + 0.5
         scale = torch.rand(E, 1, device=dev) * 0.5 + 0.1
