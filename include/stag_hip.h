@@ -582,6 +582,33 @@ int stag_normal_kl_bwd(const float* loc, const float* log_scale, int64_t n, cons
                        const float* p_scale, const float* g, float* dloc, float* dlog_scale, float* dp_loc,
                        float* dp_scale, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- sample-based KL against a mixture of Normals (stag/layers.py:141-143) ---------------------------------------
+ * The reference's fallback when torch has no closed form for (q_a, p_a) — a MixtureSameFamily prior of Normals:
+ *     q_a.log_prob(w).sum(-1).mean() - p_a.log_prob(w).sum(-1).mean()      on the forward's [E, Dn] sample w.
+ * stag_sample_kl redraws that sample from the counters instead (the draw of stag_agg_fwd / stag_noise_materialize at
+ * the same spec: position pos_base + (nidx ? nidx[p] : p), chunk chunk_base + k / 4, parameters by edge id, relu,
+ * p1_log, *epoch), and for every CSR position p and channel k < Dn forms
+ *     t = log N(w; loc, s) - logsumexp_j(mix_logw[j] + log N(w; mix_loc[j], mix_scale[j]))
+ * in registers (the maximum is subtracted inside the logsumexp):  kl_mean[0] = sum_{p,k} t / n_edges.
+ * mix_logw (the logarithms of the normalised weights), mix_loc, mix_scale: device arrays of K floats,
+ * 1 <= K <= STAG_KL_MAX_COMPONENTS, read by the kernel — no host round trip, the call can be captured in a hipGraph.
+ * dp0, dp1 (each may be NULL; both NULL: no gradient work): d kl_mean / d p0 and d kl_mean / d p1 in the parameter's
+ * own layout — [1] (SCALAR), [Dn] (PER_CHANNEL), [n_edges] by edge id (PER_EDGE1) — w.r.t. the LOG-scale when p1_log.
+ * Total derivatives: the direct part plus the part through the reparameterised sample (dw/dp of the draw, zero where
+ * relu clipped).  One launch walks the positions flat (no plan: a hub row is no different), one Philox block per 4
+ * channels; a second small one adds the block partials in `workspace` in index order, in double.  No floating-point
+ * atomics: two calls on the same inputs are bit-identical.
+ * STAG_ENOSYS (the caller keeps the materialised route): a kind other than NORMAL; in_norm; PER_EDGE parameters; p1_log
+ * with PER_CHANNEL.  (Positions may pass a 2^32 boundary: they are formed in 64 bits, as stag_noise_materialize forms
+ * them.)  STAG_EINVAL: K < 1 or K > 8; Dn <= 0; n_edges == 0; a NULL
+ * mix_* / kl_mean / workspace; deriv != 0; a csr or a spec that stag_noise_materialize refuses.  STAG_ENOMEM: workspace
+ * shorter than stag_sample_kl_workspace_bytes(n_edges, Dn).  Every argument is checked before any device work.   */
+#define STAG_KL_MAX_COMPONENTS 8
+size_t stag_sample_kl_workspace_bytes(int64_t n_edges, int32_t Dn);
+int stag_sample_kl(const stag_csr* csr, const stag_noise_spec* spec, int32_t Dn,
+                   const float* mix_logw, const float* mix_loc, const float* mix_scale, int32_t K,
+                   float* kl_mean, float* dp0, float* dp1, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Attention dropout of a GAT call (stag/zoo/gat.py:122: `attn_drop(edge_softmax(...))`, 0.6 in the reference's GAT
  * scripts): a[e,h] -> a[e,h] * keep[e,h] / keep_prob after the softmax, keep[e,h] = u < keep_prob with u the uniform
  * of the mask's OWN Philox stream (seed, offset (+ *epoch)) at (global forward position, head) — regenerated in the

@@ -21,6 +21,7 @@ REDUCE_SUM, REDUCE_MEAN = 0, 1
 DTYPE_F16, DTYPE_BF16 = 1, 2   # STAG_DTYPE_* (stag_agg_fwd_half)
 GAT_BWD_ROWDOT, GAT_BWD_SOURCE, GAT_BWD_DER = 1, 2, 4   # STAG_GAT_BWD_* (stag_gat_bwd_stages)
 HEAVY_LEN = 16   # STAG_HEAVY_LEN (include/stag_hip.h)
+KL_MAX_COMPONENTS = 8   # STAG_KL_MAX_COMPONENTS (stag_sample_kl)
 XCD_HEADER, XCD_STRIPES, XCD_FINE_MAX = 32, 8, 16   # STAG_XCD_HEADER, STAG_XCD_STRIPES, STAG_XCD_FINE_MAX
 # STAG_BLOCK_EDGES / STAG_BLOCK_UNITS of include/stag_hip.h (the environment override pairs with a build variant of the
 # library compiled with the same -D values: A/B tooling only)
@@ -162,6 +163,10 @@ def bind(path):
                                     _vp, _vp, _vp, C.c_size_t, _vp]
     l.stag_normal_kl_fwd.argtypes = [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     l.stag_normal_kl_bwd.argtypes = [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
+    l.stag_sample_kl_workspace_bytes.restype = C.c_size_t
+    l.stag_sample_kl_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    l.stag_sample_kl.argtypes = [C.POINTER(Csr), C.POINTER(NoiseSpec), C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp,
+                                 _vp, C.c_size_t, _vp]
     l.stag_coldot_workspace_bytes.restype = C.c_size_t
     l.stag_coldot_workspace_bytes.argtypes = [C.c_int32]
     l.stag_coldot.argtypes = [_vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp,

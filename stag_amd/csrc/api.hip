@@ -178,6 +178,198 @@ __global__ __launch_bounds__(256) void noise_materialize_kernel(const NoiseArgs 
   }
 }
 
+// ---- sample-based KL against a mixture of Normals (stag_sample_kl; stag/layers.py:141-143) -------------------------
+// The [E, Dn] sample of the forward is redrawn from the counters and log q(w) - log p(w) is formed in registers:
+//     t = log N(w; loc, s) - logsumexp_j(logw_j + log N(w; m_j, s_j))        (the 1/2 log 2 pi terms cancel)
+// together with its total derivatives w.r.t. q's two parameters (the direct part plus the part through w):
+//     dt/dw = -(w - loc) / s^2 + sum_j r_j (w - m_j) / s_j^2,   r_j: the responsibilities of w
+//     dt/dloc = (w - loc) / s^2 + dt/dw dw/dloc,   dt/ds = ((w - loc)^2 / s^2 - 1) / s + dt/dw dw/ds   (x s for a log-scale)
+// The walk is flat over the CSR positions (a hub row is no different from any other, so there is no plan): a team of
+// LPE lanes per position, 4 channels (one Philox block) per lane, block x takes positions x * (256 / LPE) + team,
+// + gridDim.x * (256 / LPE), ...  EDGE ([E, 1] parameters): the team walks the channel tiles itself and adds an edge's
+// Dn terms (team_sum).  Otherwise block y owns one tile of channels and a lane keeps its 4 channels' sums.
+// Every block leaves its partial sums in the workspace; sample_kl_final_kernel adds them.  No atomics.
+constexpr int kKlBlocks = 1024;
+
+struct SampleKlArgs {
+  NoiseArgs n;              // (n.w, the plan and norm_scale are not used)
+  int64_t n_edges;
+  const float* mix_logw;
+  const float* mix_loc;
+  const float* mix_scale;
+  int32_t K;
+  int32_t want_grad;
+  float inv_e;              // 1 / n_edges: per-edge gradients are finished here
+  float* part;              // [3][blocks]: the value's partials, then (SCALAR) those of the two gradients
+  float* cols;              // [gridDim.x][2][Dn]: the partial gradient rows (PER_CHANNEL)
+  float* dp0;               // [E] by edge id (PER_EDGE1), either may be null
+  float* dp1;
+};
+
+// the sum over the block's 256 threads in a fixed order (a butterfly per wave, then the 4 waves in order); thread 0
+__device__ __forceinline__ float kl_block_sum(float v, float* wave_part) {
+  v = team_sum<64>(v);
+  __syncthreads();      // (wave_part is reused from one sum to the next)
+  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((wave_part[0] + wave_part[1]) + wave_part[2]) + wave_part[3];
+}
+
+// KMAX: the components the unrolled mixture loops provide for (b.K <= KMAX).  2 — the prior the reference's script
+// builds — keeps the mixture's constants and the Philox key in SGPRs; 8 has to park some of them in VGPR lanes.
+template <int LPE, bool EDGE, int KMAX>
+__device__ __forceinline__ void sample_kl_body(const SampleKlArgs& b) {
+  const NoiseArgs& a = b.n;
+  constexpr int TPB = 256 / LPE;
+  __shared__ float red[2][256][4];
+  __shared__ float wave_part[4];
+  const int c = threadIdx.x % LPE, team = threadIdx.x / LPE;
+  const int nchunk = (a.Dn + 3) / 4;
+  const int ntile = EDGE ? (nchunk + LPE - 1) / LPE : 1;
+  const PhiloxKey key = resolve_epoch(a.key);
+  const bool logs = (a.nflags & kFlagLogScale) != 0;
+  // the mixture, read uniformly: c_j = logw_j - log s_j, m_j, 1 / s_j
+  float mc[KMAX], mm[KMAX], mi[KMAX];
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j) {
+    mc[j] = mm[j] = mi[j] = 0.f;
+    if (j < b.K) {
+      const float s = b.mix_scale[j];
+      mc[j] = b.mix_logw[j] - __logf(s);
+      mm[j] = b.mix_loc[j];
+      mi[j] = __builtin_amdgcn_rcpf(s);
+    }
+  }
+  float val = 0.f, a0[4] = {0.f, 0.f, 0.f, 0.f}, a1[4] = {0.f, 0.f, 0.f, 0.f};
+  const int64_t step = (int64_t)gridDim.x * TPB;
+  for (int64_t pp = (int64_t)blockIdx.x * TPB + team; pp < b.n_edges; pp += step) {
+    const int p = (int)pp;
+    const int64_t ed = a.eid ? a.eid[p] : p;
+    float e0 = 0.f, e1 = 0.f;
+    for (int tile = 0; tile < ntile; ++tile) {
+      const uint32_t chunk = (EDGE ? tile : (int)blockIdx.y) * LPE + c;
+      const int k0 = (int)chunk * 4;
+      if (k0 >= a.Dn) continue;
+      float pa[4], pb[4], w[4], d0[4], d1[4];
+      edge_params4(a, ed, k0, pa, pb);
+      edge_w4_grad_p(a, key, p, chunk, pa, pb, w, d0, d1);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const bool in = k0 + q < a.Dn;          // (a tail channel has no parameters: whatever it computes is dropped)
+        const float is = __builtin_amdgcn_rcpf(pb[q]);
+        const float u = (w[q] - pa[q]) * is;
+        float e[KMAX], mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) {
+          if (j < b.K) {
+            const float uj = (w[q] - mm[j]) * mi[j];
+            e[j] = mc[j] - 0.5f * (uj * uj);
+            mx = fmaxf(mx, e[j]);
+          }
+        }
+        float S = 0.f, R = 0.f;
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) {
+          if (j < b.K) {
+            const float x = __expf(e[j] - mx);
+            S += x;
+            R += x * (((w[q] - mm[j]) * mi[j]) * mi[j]);
+          }
+        }
+        const float t = (-__logf(pb[q]) - 0.5f * (u * u)) - (mx + __logf(S));
+        val += in ? t : 0.f;
+        if (b.want_grad) {
+          const float A = u * is;                                        // (w - loc) / s^2
+          const float G = R * __builtin_amdgcn_rcpf(S) - A;              // dt/dw
+          const float B = (u * u - 1.0f) * (logs ? 1.0f : is);           // dt/ds | dt/dlog s at fixed w
+          const float g0 = in ? A + G * d0[q] : 0.f;
+          const float g1 = in ? B + G * d1[q] : 0.f;
+          if (EDGE) { e0 += g0; e1 += g1; }
+          else { a0[q] += g0; a1[q] += g1; }
+        }
+      }
+    }
+    if (EDGE && b.want_grad) {
+      e0 = team_sum<LPE>(e0);
+      e1 = team_sum<LPE>(e1);
+      if (c == 0) {
+        if (b.dp0) b.dp0[ed] = e0 * b.inv_e;
+        if (b.dp1) b.dp1[ed] = e1 * b.inv_e;
+      }
+    }
+  }
+  const int64_t nb = (int64_t)gridDim.x * gridDim.y, bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+  val = kl_block_sum(val, wave_part);
+  if (threadIdx.x == 0) b.part[bid] = val;
+  if (EDGE || !b.want_grad) return;
+  if (a.pmode == 0) {       // one value per parameter
+    const float s0 = kl_block_sum((a0[0] + a0[1]) + (a0[2] + a0[3]), wave_part);
+    const float s1 = kl_block_sum((a1[0] + a1[1]) + (a1[2] + a1[3]), wave_part);
+    if (threadIdx.x == 0) { b.part[nb + bid] = s0; b.part[2 * nb + bid] = s1; }
+    return;
+  }
+  // a row per parameter: the teams of the block, added in team order by the lanes of team 0
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { red[0][threadIdx.x][q] = a0[q]; red[1][threadIdx.x][q] = a1[q]; }
+  __syncthreads();
+  const int k0 = ((int)blockIdx.y * LPE + c) * 4;
+  if (team == 0) {
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float s = 0.f;
+        for (int r = 0; r < TPB; ++r) s += red[o][r * LPE + c][q];
+        if (k0 + q < a.Dn) b.cols[((int64_t)blockIdx.x * 2 + o) * a.Dn + k0 + q] = s;
+      }
+  }
+}
+
+template <int LPE, bool EDGE>
+__global__ __launch_bounds__(256) void sample_kl_kernel2(const SampleKlArgs b) { sample_kl_body<LPE, EDGE, 2>(b); }
+template <int LPE, bool EDGE>
+__global__ __launch_bounds__(256) void sample_kl_kernel8(const SampleKlArgs b) {
+  sample_kl_body<LPE, EDGE, STAG_KL_MAX_COMPONENTS>(b);
+}
+
+// Blocks [0, nq): quantity q = the sum of part[q * n .. q * n + n) — thread t adds its contiguous share in index order,
+// thread 0 the 256 shares in thread order, all in double — times 1 / n_edges, to out_q[0] (q = 0: kl_mean; 1, 2: the
+// gradients of SCALAR parameters).  Blocks from nq on (PER_CHANNEL): 4 columns (o, k) of cols each, 64 lanes a column.
+__global__ __launch_bounds__(256) void sample_kl_final_kernel(const float* part, int64_t n, int nq, const float* cols,
+                                                              int nbx, int Dn, double inv_e, float* kl_mean,
+                                                              float* dp0, float* dp1) {
+  __shared__ double red[256];
+  if ((int)blockIdx.x < nq) {
+    const int q = blockIdx.x;
+    const int64_t G = (n + 255) / 256, lo = threadIdx.x * G, hi = lo + G < n ? lo + G : n;
+    double s = 0.0;
+    for (int64_t i = lo; i < hi; ++i) s += (double)part[q * n + i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    float* out = q == 0 ? kl_mean : (q == 1 ? dp0 : dp1);
+    if (threadIdx.x == 0 && out) {
+      double tot = 0.0;
+      for (int i = 0; i < 256; ++i) tot += red[i];
+      out[0] = (float)(tot * inv_e);
+    }
+    return;
+  }
+  const int l = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int col = ((int)blockIdx.x - nq) * 4 + g;
+  const int o = col / Dn, k = col - o * Dn;
+  const int G = (nbx + 63) / 64, lo = l * G, hi = lo + G < nbx ? lo + G : nbx;
+  double s = 0.0;
+  if (col < 2 * Dn)
+    for (int i = lo; i < hi; ++i) s += (double)cols[((int64_t)i * 2 + o) * Dn + k];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  float* out = o == 0 ? dp0 : dp1;
+  if (l == 0 && col < 2 * Dn && out) {
+    double tot = 0.0;
+    for (int i = 0; i < 64; ++i) tot += red[g * 64 + i];
+    out[k] = (float)(tot * inv_e);
+  }
+}
+
 // dw[eid, k] = D[p,k] * sscale[u] * x[u,k] * g[v,k]   (stag_agg_bwd_w)
 // A team of LPE lanes per unit of the plan, 4 channels per lane, two edges in flight; the row
 // of g is the unit's own row.  D = 1 (explicit weights), one regenerated derivative
@@ -1056,6 +1248,71 @@ int stag_noise_materialize(const stag_csr* csr, const stag_plan* plan, const sta
   const dim3 grid((a.n_units + 256 / lpe - 1) / (256 / lpe), (nchunk + lpe - 1) / lpe);
   hipStream_t s = (hipStream_t)stream;
   STAG_LPE_DISPATCH(noise_materialize_kernel, lpe, vec, grid, s, a);
+  return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
+}
+
+}  // extern "C" (reopened below)
+namespace {
+// the grid of sample_kl_kernel: lanes per position, blocks along the positions, blocks along the channel tiles
+void sample_kl_shape(int64_t n_edges, int32_t Dn, int& lpe, int64_t& nbx, int64_t& nby) {
+  const int nchunk = (Dn + 3) / 4;
+  lpe = lanes_for(nchunk, 1);
+  const int tpb = 256 / lpe;
+  nbx = std::min<int64_t>(kKlBlocks, (n_edges + tpb - 1) / tpb);
+  nby = (nchunk + lpe - 1) / lpe;
+}
+}  // namespace
+extern "C" {
+
+// 3 partials per block (the value, the two gradients of SCALAR parameters) and a pair of [Dn] rows per block along
+// the positions (PER_CHANNEL); whichever parameter mode the call then has
+size_t stag_sample_kl_workspace_bytes(int64_t n_edges, int32_t Dn) {
+  if (n_edges <= 0 || Dn <= 0) return 0;
+  int lpe;
+  int64_t nbx, nby;
+  sample_kl_shape(n_edges, Dn, lpe, nbx, nby);
+  return (size_t)(3 * nbx * nby + 2 * nbx * (int64_t)Dn) * sizeof(float);
+}
+
+int stag_sample_kl(const stag_csr* csr, const stag_noise_spec* spec, int32_t Dn, const float* mix_logw,
+                   const float* mix_loc, const float* mix_scale, int32_t K, float* kl_mean, float* dp0, float* dp1,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = check_csr(csr);
+  if (rc) return rc;
+  if (Dn <= 0) return STAG_EINVAL;
+  rc = check_spec(spec, csr->n_edges, Dn);
+  if (rc) return rc;
+  if (!mix_logw || !mix_loc || !mix_scale || !kl_mean || !workspace) return STAG_EINVAL;
+  if (K < 1 || K > STAG_KL_MAX_COMPONENTS || csr->n_edges == 0 || spec->deriv != 0) return STAG_EINVAL;
+  if (spec->kind != STAG_NOISE_NORMAL || spec->in_norm || spec->param_mode == STAG_PARAM_PER_EDGE) return STAG_ENOSYS;
+  // (check_positions has nothing to refuse here: the kernel forms every global position in 64 bits, as
+  //  stag_noise_materialize does, so a call may pass a 2^32 boundary; check_spec bounds the counter word)
+  if (workspace_bytes < stag_sample_kl_workspace_bytes(csr->n_edges, Dn)) return STAG_ENOMEM;
+  SampleKlArgs b{};
+  NoiseArgs& a = b.n;
+  a.indptr = csr->indptr; a.eid = csr->eid; a.nidx = csr->nidx; a.n_rows = csr->n_dst; a.Dn = Dn;
+  fill_spec(a, spec, 0);
+  int lpe;
+  int64_t nbx, nby;
+  sample_kl_shape(csr->n_edges, Dn, lpe, nbx, nby);
+  const bool edge = a.pmode == STAG_PARAM_PER_EDGE1;
+  if (edge) nby = 1;                                      // the team walks the channel tiles itself
+  const int64_t nb = nbx * nby;
+  b.n_edges = csr->n_edges;
+  b.mix_logw = mix_logw; b.mix_loc = mix_loc; b.mix_scale = mix_scale; b.K = K;
+  b.want_grad = (dp0 || dp1) ? 1 : 0;
+  b.inv_e = 1.0f / (float)csr->n_edges;
+  b.part = static_cast<float*>(workspace);
+  b.cols = b.part + 3 * nb;
+  b.dp0 = dp0; b.dp1 = dp1;
+  const dim3 grid((unsigned)nbx, (unsigned)nby);
+  hipStream_t s = (hipStream_t)stream;
+  if (K <= 2) STAG_LPE_DISPATCH(sample_kl_kernel2, lpe, edge, grid, s, b);
+  else STAG_LPE_DISPATCH(sample_kl_kernel8, lpe, edge, grid, s, b);
+  const bool rows = b.want_grad && a.pmode == STAG_PARAM_PER_CHANNEL;
+  const int nq = (b.want_grad && a.pmode == STAG_PARAM_SCALAR) ? 3 : 1;
+  hipLaunchKernelGGL(sample_kl_final_kernel, dim3(nq + (rows ? (2 * Dn + 3) / 4 : 0)), dim3(256), 0, s, b.part, nb, nq,
+                     b.cols, (int)nbx, Dn, 1.0 / (double)csr->n_edges, kl_mean, dp0, dp1);
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 

@@ -253,6 +253,13 @@ class StagLayer(torch.nn.Module):
                 self.q_a.base_distribution, self.p_a.base_distribution).mean()
         except Exception:   # the reference falls back on ANY failure (stag/layers.py:141)
             self._kl_sampled = True
+            h = self._edge_weight_handle
+            if isinstance(h, EdgeNoise):
+                # a mixture-of-Normals prior: the estimate and its gradients from one pass that redraws the sample
+                # from the counters (stag_sample_kl); the handle stays a descriptor, nothing [E, Dn]-sized exists
+                from . import ops as _ops
+                if _ops.sampled_kl_why_not(h, self.p_a) is None:
+                    return _ops.sampled_kl_mean(h, self.p_a)
             w = self._edge_weight_sample
             return (self.q_a.log_prob(w).sum(dim=-1).mean()
                     - self.p_a.log_prob(w).sum(dim=-1).mean())

@@ -682,6 +682,128 @@ def normal_kl_mean(loc, log_scale, p_loc, p_scale):
     return _NormalKlMean.apply(loc, log_scale, p_loc, p_scale)
 
 
+# ---- the sample-based KL fallback against a mixture prior (stag/layers.py:141-143) -----------------------------------
+# stag_sample_kl | the composed route (EdgeNoise.materialize(), both log_probs as eager torch over [E, Dn] and, for the
+# mixture, [E, Dn, K]).  The value is the same within tolerance either way: a speed and memory decision only.  True
+# because the fused training step measures faster at the arxiv shape (GCN 128 -> 128, 2-component prior,
+# profiles/r11/sample_kl.txt): 1.41 against 19.06 ms with learned scalars, 1.78 against 19.46 ms with [E, 1] amortised
+# heads (two repeats of the composed step differ by 0.01-0.04 ms); peak allocation of a step 0.5 against 8.8 GB.
+SAMPLED_KL_FUSED = True
+
+
+def sampled_kl_why_not(noise, prior):
+    """The first reason StagLayer.kl_divergence keeps the composed route for its sample-based estimate, or None: the
+    estimate and its gradients come from one stag_sample_kl launch and `noise` stays a descriptor.  One clause per
+    refusal of the entry point (include/stag_hip.h) and per case that has no fused form."""
+    if not SAMPLED_KL_FUSED:
+        return "switch"
+    if not isinstance(noise, EdgeNoise) or noise.kind != _lib.NOISE_NORMAL:
+        return "noise kind"
+    if noise.in_norm:
+        return "in-norm"
+    if noise.param_mode == _lib.PARAM_PER_EDGE:
+        return "per-edge parameters"
+    if noise.deriv:
+        return "derivative selector"
+    if noise.n_samples != 1:
+        return "monte-carlo"
+    graph = noise.graph
+    if getattr(graph, "is_shard", False):
+        return "shard"
+    if graph.number_of_edges() == 0:
+        return "no edges"
+    if torch.compiler.is_compiling():
+        return "compiling"
+    D = torch.distributions
+    if not isinstance(prior, D.MixtureSameFamily) or type(prior.component_distribution) is not D.Normal:
+        return "prior"
+    comp = prior.component_distribution
+    tensors = (prior.mixture_distribution.logits, comp.loc, comp.scale)
+    if len(comp.batch_shape) != 1 or not 1 <= comp.batch_shape[0] <= _lib.KL_MAX_COMPONENTS:
+        return "prior"
+    if any(t.shape != comp.batch_shape for t in tensors):
+        return "prior"
+    dev = torch.device(graph.device)
+    if any(t.device != dev for t in tensors):
+        return "prior device"
+    if any(t.requires_grad for t in tensors):
+        return "prior gradients"
+    if dev.type != "cuda":
+        return "device"
+    return None
+
+
+def _sample_kl_raw(noise, mixture, want_grad):
+    """One stag_sample_kl: (kl_mean [1], d kl_mean / d p0, d kl_mean / d p1), the gradients in the layout of the
+    descriptor's parameters ([1], [Dn] or [E, 1]) or None."""
+    csrv = noise.graph.csr
+    dev = _lib.require_device(csrv.indptr)
+    E, dn = csrv.n_edges, noise.dn
+    comp = mixture.component_distribution
+    logw = _f32c(mixture.mixture_distribution.logits.detach())
+    mloc, mscale = _f32c(comp.loc.detach()), _f32c(comp.scale.detach())
+    _lib.require_device(logw, mloc, mscale, csrv.indptr)
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    d0 = d1 = None
+    if want_grad:
+        shape = {_lib.PARAM_SCALAR: (1,), _lib.PARAM_PER_CHANNEL: (dn,), _lib.PARAM_PER_EDGE1: (E, 1)}[noise.param_mode]
+        d0 = torch.empty(shape, dtype=torch.float32, device=dev)
+        d1 = torch.empty(shape, dtype=torch.float32, device=dev)
+    nbytes = _lib.lib().stag_sample_kl_workspace_bytes(E, dn)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    spec, cs = noise.spec(), csrv.struct()
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_sample_kl(C.byref(cs), C.byref(spec), dn, _lib.ptr(logw), _lib.ptr(mloc), _lib.ptr(mscale),
+                                       logw.numel(), _lib.ptr(out), _lib.ptr(d0), _lib.ptr(d1), _lib.ptr(ws), nbytes,
+                                       _lib.stream_of(dev))
+    _lib.check(rc, "stag_sample_kl")
+    return out, d0, d1
+
+
+class _SampledKlMean(torch.autograd.Function):
+    """q.log_prob(w).sum(-1).mean() - mixture.log_prob(w).sum(-1).mean() on the sample a descriptor stands for
+    (stag/layers.py:141-143), differentiated through the reparameterised draw as the reference's `rsample` is.  The
+    forward launch returns the value AND both parameter gradients (two tensors of the parameters' size, never [E, Dn]);
+    the backward scales them by the incoming gradient: no second launch."""
+
+    @staticmethod
+    def forward(ctx, p0, p1, noise, mixture):
+        out, d0, d1 = _sample_kl_raw(noise, mixture, True)
+        ctx.save_for_backward(d0, d1)
+        ctx.shapes = (p0.shape, p1.shape)
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        grads = [None, None]
+        for i, d in enumerate(ctx.saved_tensors):
+            if not ctx.needs_input_grad[i]:
+                continue
+            d, shape = d * g, ctx.shapes[i]
+            if d.numel() == shape.numel():
+                grads[i] = d.reshape(shape)
+            elif shape.numel() == 1:                 # a one-element parameter that travelled as a row
+                grads[i] = d.sum().reshape(shape)
+            else:
+                grads[i] = d.sum_to_size(shape)
+        return grads[0], grads[1], None, None
+
+
+def sampled_kl_mean(noise, mixture):
+    """The sample-based KL estimate of a Normal `noise` descriptor against a MixtureSameFamily of Normals, from the
+    counters (stag_sample_kl): an autograd function over noise.grad_params as they are, the plain value when there are
+    none.  sampled_kl_why_not(noise, mixture) says when it applies."""
+    why = sampled_kl_why_not(noise, mixture)
+    if why is not None and why != "switch":
+        raise ValueError(f"sampled_kl_mean does not apply: {why}")
+    if noise.grad_params is not None and torch.is_grad_enabled():
+        dev = noise.graph.device
+        p0, p1 = (torch.as_tensor(p, dtype=torch.float32, device=dev) for p in noise.grad_params)
+        if p0.requires_grad or p1.requires_grad:
+            return _SampledKlMean.apply(p0, p1, noise, mixture)
+    return _sample_kl_raw(noise, mixture, False)[0].reshape(())
+
+
 def _bwd_w_raw(csrv, x, g, D, src_scale, broadcast_x=False, spec=None, reduce_k=False, both=False,
                seg_len=DEFAULT_SEG_LEN):
     """stag_agg_bwd_w over the plan's units.  both=True: (d/dp0, d/dp1) of a Normal | Uniform spec
