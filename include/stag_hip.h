@@ -157,8 +157,14 @@ typedef struct stag_plan {
   const stag_unit* units;      /* [n_units], 16-byte aligned                       */
   const int32_t* long_rows;    /* [n_long]   row ids, largest in-degree first      */
   const int32_t* long_seg_ptr; /* [n_long+1] segment-id range of each long row     */
-  int32_t* seg_counters;       /* [n_long * ceil(D / 256)] arrival counters: ZERO on
-                                  entry, left zero by every completed call         */
+  int32_t* seg_counters;       /* arrival counters: ZERO on entry, left zero by every completed call.  With
+                                  T = ceil(D / 256) channel tiles: T * n_long ints (a counter per long row and tile),
+                                  and when n_seg > 16, for the stag_agg_* entry points that use counters, T * n_seg
+                                  more behind them: a row of more than 16 segments is added group by group
+                                  (16 segments a group), and the group that starts at segment s counts its arrivals
+                                  at [T * n_long + tile * n_seg + s].  STAG_COMBINE_GROUPS=0 in the environment (read
+                                  at each call) keeps one team per row and the first T * n_long ints; so do the GAT
+                                  entry points.  The size is the caller's to get right: nothing here can check it */
   float* workspace;            /* >= stag_plan_workspace_bytes(); one call at a
                                   time may use a plan's workspace and counters     */
   size_t workspace_bytes;
@@ -199,6 +205,8 @@ int stag_plan_count(const int32_t* indptr_host, int32_t n_dst, int32_t seg_len,
 int stag_plan_fill(const int32_t* indptr_host, int32_t n_dst, int32_t seg_len,
                    stag_unit* units_host, int32_t* long_rows_host,
                    int32_t* long_seg_ptr_host);
+/* n_seg rows of D (in-norm: 2 D) floats for the segment partials; when n_seg > 16, 2 * (2 * ((n_seg - 1) / 16) + 2)
+ * rows more: the (group sum, residual) pairs of the rows that are added group by group.  At most 16 segments: as before. */
 size_t stag_plan_workspace_bytes(int32_t n_seg, int32_t D, int32_t in_norm);
 /* Batches of consecutive units for the workgroup-cooperative kernels: block_ptr_host[n_blocks+1]
  * (NULL: count only), greedy in plan order: a batch closes before it would exceed max_edges edges

@@ -113,11 +113,15 @@ struct AggArgs {
   const int32_t* long_seg_ptr;
   int32_t n_long;
   int32_t n_seg;           // units[0, n_seg) are segments, the rest whole rows
-  int32_t* seg_counters;   // [n_long] arrival counters, zero between launches
-  float* ws;               // [n_seg][ws_stride]: D partial sums, then D weight sums if in_norm
+  int32_t* seg_counters;   // [tiles][n_long] arrival counters of the rows, then [tiles][n_seg] of the groups of
+                           // segments (at a group's first segment); zero between launches
+  float* ws;               // [n_seg][ws_stride]: D partial sums, then D weight sums if in_norm; then the group
+                           // pairs [combine_pair_slots(n_seg)][2][ws_stride]: (group sums | their residuals)
   int32_t ws_stride;
   uint32_t ws_bytes;
   uint32_t idx_bytes;      // extent of indices when it fits a buffer descriptor (< 2^30 edges), else 0
+  int32_t combine_groups;  // > 0: rows of more than kCombineGroup segments are added group by group, and this is where
+                           // the group counters start in seg_counters: tiles * n_long (agg_launch_impl); 0: one team a row
 };
 
 __device__ __forceinline__ void load4(const float* p, int k0, int D, bool vec, float (&v)[4]) {
@@ -231,6 +235,53 @@ __device__ __forceinline__ void two_level_sum(const float* ws, int ws_stride, in
   for (int q = 0; q < 4; ++q) sum[q] -= comp[q];
 }
 
+// The same tree spread over teams (agg_unit's segment tail): a row of more than kCombineGroup segments has its groups
+// added by the teams that complete them, and each group leaves the pair (group sum, residual) of kahan_sum_partials
+// in the workspace behind the partials.  Pair slots are cut on the GLOBAL segment index, so nothing per row is
+// planned: a row's first group (first segment gs == s0) takes slot 2 (gs >> 4) + 1, its later groups 2 (gs >> 4).
+// Within a row the group starts are 16 apart, and only rows of at least 17 segments take slots, so the first groups of
+// two rows, and the later groups of any rows, are at least 16 segments apart too: no two groups share a slot.
+__host__ __device__ __forceinline__ int combine_pair_slot(int gs, int s0) { return 2 * (gs / kCombineGroup) + (gs == s0 ? 1 : 0); }
+__host__ __device__ __forceinline__ int combine_pair_slots(int n_seg) {
+  return n_seg > kCombineGroup ? 2 * ((n_seg - 1) / kCombineGroup) + 2 : 0;
+}
+// The second level of two_level_sum on published pairs: `pairs` = the pair region at this sum's column, NP pairs (2 NP
+// rows) in flight.  A group that does not exist is skipped, not added as zero: a fold step also applies the compensation.
+template <int NP, bool VEC>
+__device__ __forceinline__ void fold_group_pairs(const float* pairs, int ws_stride, int s0, int s1, int k0, int D,
+                                                 float (&sum)[4]) {
+  float comp[4] = {0.f, 0.f, 0.f, 0.f};
+  sum[0] = sum[1] = sum[2] = sum[3] = 0.f;
+#pragma unroll 1
+  for (int g0 = s0; g0 < s1; g0 += kCombineGroup * NP) {
+    float t[NP][2][4];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const int gs = g0 + i * kCombineGroup;
+      if (gs < s1) {
+        const float* p = pairs + (int64_t)combine_pair_slot(gs, s0) * (2 * ws_stride);
+        load4(p, k0, D, VEC, t[i][0]);
+        load4(p + ws_stride, k0, D, VEC, t[i][1]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      if (g0 + i * kCombineGroup < s1) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          comp[q] += t[i][1][q];                    // true group sum = group sum - residual
+          const float y = t[i][0][q] - comp[q];
+          const float n = sum[q] + y;
+          comp[q] = (n - sum[q]) - y;
+          sum[q] = n;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) sum[q] -= comp[q];
+}
+
 // epilogue shared by whole-row units and the last-arriver combine
 __device__ __forceinline__ void agg_epilogue_to(const AggArgs& a, float* out, float* norm_scale_out, int v, int deg,
                                                 int k0, bool vec, float (&acc)[4], const float (&wsum)[4]);
@@ -265,6 +316,77 @@ __device__ __forceinline__ void agg_epilogue_extra(const AggArgs& a, float* out,
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc[j] *= dv;
   store4(out + (int64_t)v * a.ldo, k0, a.D, vec, acc);
+}
+
+// A long row of more than one group of segments (agg_unit's segment tail; the partial of segment `slot` is stored and
+// drained): the same producer / consumer protocol one level down, so that as many teams add the row as it has groups.
+// The segment takes its ticket on its GROUP's counter; the team that draws the group's last ticket acquires, Kahan-sums
+// the group's partials in segment order (every column of the workspace row: outputs and weight sums), publishes
+// (group sum, residual) write-through, drains, and stands for its group at the row's counter, which for such a row counts
+// groups; the team that draws the row's last ticket acquires, folds the pairs in group order and runs the epilogue.
+// One team adding the 203 partials of the arxiv hub, 8 in flight, is 26 dependent round trips, 52 with in-norm (DESIGN.md
+// 4.1); this is 2 per column of one group, the groups side by side, and 4 for the fold of 13 pairs.
+#ifndef STAG_COMBINE_GROUP_NF
+#define STAG_COMBINE_GROUP_NF 8   // partials in flight where a group is added; half as many pairs (two rows each) in the fold
+#endif
+template <bool VEC, int LPE, int PEDGE, int SLOTS, int NOUT, bool WN>
+__device__ __forceinline__ void combine_grouped(const AggArgs& a, __amdgpu_buffer_rsrc_t rws, int r, int slot, int s0,
+                                                int s1, int c, int sl, int k0, int lane0) {
+  constexpr int NG = STAG_COMBINE_GROUP_NF;
+  const int gs = s0 + (slot - s0) / kCombineGroup * kCombineGroup, ge = min(gs + kCombineGroup, s1);
+  // group counters: behind the row counters of all channel tiles, [tile][segment index], at the group's first segment
+  int32_t* gcounter = a.seg_counters + a.combine_groups + (int64_t)blockIdx.y * a.n_seg + gs;
+  int ticket = 0;
+  if (c == 0 && sl == 0)
+    ticket = __hip_atomic_fetch_add(gcounter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  ticket = __builtin_amdgcn_ds_bpermute(lane0, ticket);
+  if (ticket != (ge - gs) - 1) return;
+  if (SLOTS > 1 && sl != 0) return;     // any unit may add a group, one of its edge slots does: the partials are added
+                                        // one after the other
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (c == 0) *gcounter = 0;            // leave the counter ready for the next call
+  const int ncol = NOUT * ((PEDGE != 3 && PEDGE != 4 && a.in_norm) ? 2 : 1);     // ws_stride / D
+  const uint32_t poff = (uint32_t)a.n_seg * ((uint32_t)a.ws_stride * 4u) +
+                        (uint32_t)combine_pair_slot(gs, s0) * ((uint32_t)a.ws_stride * 8u) + (uint32_t)k0 * 4u;
+#pragma unroll 1
+  for (int j = 0; j < ncol; ++j) {
+    float gsum[4], gres[4];
+    kahan_sum_partials<NG, VEC>(a.ws + j * a.D, a.ws_stride, gs, ge, k0, a.D, gsum, gres);
+    store4_sc1(rws, poff + (uint32_t)(j * a.D) * 4u, k0, a.D, VEC, gsum);
+    store4_sc1(rws, poff + (uint32_t)(a.ws_stride + j * a.D) * 4u, k0, a.D, VEC, gres);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  int32_t* counter = a.seg_counters + (int64_t)blockIdx.y * a.n_long + r;
+  ticket = 0;
+  if (c == 0) ticket = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  ticket = __builtin_amdgcn_ds_bpermute(lane0, ticket);
+  if (ticket != (s1 - s0 + kCombineGroup - 1) / kCombineGroup - 1) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (c == 0) *counter = 0;
+  const int row = a.long_rows[r];
+  const int deg = a.indptr[row + 1] - a.indptr[row];
+  // the second level of two_level_sum on the published pairs, in group order
+  const float* pairs = a.ws + (int64_t)a.n_seg * a.ws_stride;
+  float facc[4], fws[4] = {0.f, 0.f, 0.f, 0.f};
+  fold_group_pairs<NG / 2, VEC>(pairs, a.ws_stride, s0, s1, k0, a.D, facc);
+  if (PEDGE != 3 && PEDGE != 4 && a.in_norm) fold_group_pairs<NG / 2, VEC>(pairs + NOUT * a.D, a.ws_stride, s0, s1, k0, a.D, fws);
+  agg_epilogue(a, row, deg, k0, VEC, facc, fws);
+#pragma unroll
+  for (int o = 0; o < NOUT - 1; ++o) {
+    fold_group_pairs<NG / 2, VEC>(pairs + (o + 1) * a.D, a.ws_stride, s0, s1, k0, a.D, facc);
+    if constexpr (WN) {
+      fold_group_pairs<NG / 2, VEC>(pairs + (NOUT + o + 1) * a.D, a.ws_stride, s0, s1, k0, a.D, fws);
+      agg_epilogue_to(a, a.outx[o], nullptr, row, deg, k0, VEC, facc, fws);
+    } else {
+      agg_epilogue_extra(a, a.outx[o], row, deg, k0, VEC, facc);
+    }
+  }
+  // Not to be merged with the end of the one-team path: the two epilogues are the same code, and merged into one block
+  // they make the lanes of this path wait, their values live, while the other path's combine runs at ITS register peak
+  // — every wide kernel then took 82-84 VGPRs instead of 69-70, five waves per SIMD instead of seven.
+  asm volatile("; combine_grouped: done" ::: "memory");
 }
 
 // row `idx` of a row-major fp32 matrix, `koff` bytes into the row.  Narrow form: one
@@ -961,11 +1083,19 @@ __device__ __forceinline__ void agg_unit(const AggArgs& a, const int unit, const
   }
   const int s0 = a.long_seg_ptr[r], s1 = a.long_seg_ptr[r + 1];
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const int lane0 = ((int)(threadIdx.x & 63) - c - sl * LPE) << 2;   // the unit's first lane
+  // a row of more than one group of segments is added group by group, by the teams that complete the groups
+  if (a.combine_groups && (s1 - s0) > kCombineGroup) {
+    combine_grouped<VEC, LPE, PEDGE, SLOTS, NOUT, WN>(a, rws, r, slot, s0, s1, c, sl, k0, lane0);
+#ifdef STAG_TRACE
+    if (trace) trace[2] = trace[3] = wall_clock64();
+#endif
+    return;
+  }
   int ticket = 0;
   int32_t* counter = a.seg_counters + (int64_t)blockIdx.y * a.n_long + r;   // per channel tile
   if (c == 0 && sl == 0)
     ticket = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int lane0 = ((int)(threadIdx.x & 63) - c - sl * LPE) << 2;   // the unit's first lane
   ticket = __builtin_amdgcn_ds_bpermute(lane0, ticket);
 #ifdef STAG_TRACE
   if (trace) trace[2] = wall_clock64();
@@ -1244,6 +1374,13 @@ inline bool plain_enabled() {
   return !(e && e[0] == '0' && e[1] == 0);
 }
 
+// STAG_COMBINE_GROUPS=0 in the environment has one team add every long row, whatever its length (read at each launch):
+// the path rows of at most kCombineGroup segments take anyway, so the switch costs no device code.  Same bits.
+inline bool combine_groups_enabled() {
+  const char* e = getenv("STAG_COMBINE_GROUPS");
+  return !(e && e[0] == '0' && e[1] == 0);
+}
+
 // the SMALL instantiation of the plain plan-order launch at 32 lanes per row (heavy_slots_of)
 template <int KIND>
 inline void agg_launch_small(const AggArgs& a_in, bool vec, int tiles, hipStream_t s) {
@@ -1372,12 +1509,14 @@ inline void agg_launch_shape(const AggArgs& a_in, bool vec, int pedge, int tiles
 }
 
 template <int KIND>
-inline hipError_t agg_launch_impl(const AggArgs& a, bool vec, hipStream_t s) {
+inline hipError_t agg_launch_impl(const AggArgs& a_in, bool vec, hipStream_t s) {
+  AggArgs a = a_in;
   const int nchunk = (a.D + 3) / 4;
   const int pedge = (KIND < kNormal) ? 0 : a.pmode == STAG_PARAM_PER_EDGE1 ? (a.eg0 ? 3 : 1)
                     : a.pmode == STAG_PARAM_PER_EDGE ? 2 : 0;
   const int lpe = lanes_for(nchunk, 1);   // lanes per unit
   const int tiles = (nchunk + lpe - 1) / lpe;
+  if (a.combine_groups) a.combine_groups = tiles * a.n_long;    // where the group counters start (segments: n_long >= 1)
   switch (lpe) {
     case 64: agg_launch_shape<KIND, 64>(a, vec, pedge, tiles, s); break;
     case 32: agg_launch_shape<KIND, 32>(a, vec, pedge, tiles, s); break;

@@ -907,7 +907,9 @@ int stag_plan_blocks_xcd_ranges(const stag_unit* units_host, int32_t n_units, co
 
 size_t stag_plan_workspace_bytes(int32_t n_seg, int32_t D, int32_t in_norm) {
   if (n_seg <= 0 || D <= 0) return 0;
-  return (size_t)n_seg * (size_t)D * (in_norm ? 2u : 1u) * sizeof(float);
+  // a row per segment, then two rows (group sums, residuals) per pair slot of the group-wise combine (agg_kernel.hpp)
+  const size_t rows = (size_t)n_seg + 2u * (size_t)stag::combine_pair_slots(n_seg);
+  return rows * (size_t)D * (in_norm ? 2u : 1u) * sizeof(float);
 }
 
 int stag_philox_raw(uint64_t seed, uint64_t offset, int64_t pos0, int64_t n_pos, int32_t n_chunk,
@@ -1005,6 +1007,7 @@ static int agg_common(const stag_csr* csr, const stag_plan* plan, const float* x
   if (has_segs) {
     a.ws_stride = D * nout * (spec->in_norm ? 2 : 1); a.ws_bytes = (uint32_t)need;
     a.seg_counters = plan->seg_counters; a.n_seg = plan->n_seg;
+    a.combine_groups = combine_groups_enabled() ? 1 : 0;
   }
 
   // dwordx4 path needs 16-B aligned rows everywhere a float4 is formed

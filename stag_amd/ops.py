@@ -73,6 +73,26 @@ def _spec_in_norm(spec):
     return bool(spec[0][3]) if isinstance(spec, tuple) else bool(spec.in_norm)
 
 
+_COMBINE_GROUP = 16     # kCombineGroup (csrc/agg_kernel.hpp): partials per group of a long row's combine
+
+
+def _counter_count(n_long, n_seg, tiles):
+    """ints of stag_plan.seg_counters: a row counter per (channel tile, long row), then — once a row can have more
+    than one group of segments — a group counter per (channel tile, segment index), taken by a group's first segment."""
+    return max(n_long, 1) * tiles + (n_seg * tiles if n_seg > _COMBINE_GROUP else 0)
+
+
+def _plan_counters(plan_t, tiles, dev):
+    """The plan's arrival counters: one set per (channel tiles, stream) — two launches that may be in flight together
+    (different streams) must not share them; zeroed once, every completed launch leaves them zero again."""
+    key = (tiles, _lib.stream_of(dev))
+    counters = plan_t["counters"].get(key)
+    if counters is None:
+        counters = torch.zeros(_counter_count(plan_t["n_long"], plan_t["n_seg"], tiles), dtype=torch.int32, device=dev)
+        plan_t["counters"][key] = counters
+    return key, counters
+
+
 def _plan_struct(csrv, seg_len, tiles, nbytes, dev, plan_t=None, width=None, gat_width=None, drawn=False):
     """ctypes stag_plan for csrv (None when planning is off), plus the tensors it points into.
     plan_t: a sub-plan of csrv (CsrView.subplan) instead of its whole plan.  width: the row width of an aggregation
@@ -83,14 +103,7 @@ def _plan_struct(csrv, seg_len, tiles, nbytes, dev, plan_t=None, width=None, gat
     if plan_t is None:
         return None, None
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
-    # arrival counters of the long rows: one set per (channel tiles, stream) — two launches that may
-    # be in flight together (different streams) must not share them; zeroed once, every completed
-    # launch leaves them zero again
-    key = (tiles, _lib.stream_of(dev))
-    counters = plan_t["counters"].get(key)
-    if counters is None:
-        counters = torch.zeros(max(plan_t["n_long"], 1) * tiles, dtype=torch.int32, device=dev)
-        plan_t["counters"][key] = counters
+    key, counters = _plan_counters(plan_t, tiles, dev)
     order, strides, fine = csrv.xcd_order(plan_t, width, drawn) if width and plan_t.get("xcd_on") else (None, (0, 0), 0)
     units, block_ptr, n_blocks = plan_t["units"], plan_t["block_ptr"], plan_t["n_blocks"]
     if gat_width and plan_t.get("xcd_on"):
@@ -119,11 +132,7 @@ def _plan_args(csrv, plan_t, tiles, dev, width=None, drawn=False):
     """(units, long_rows, long_seg_ptr, block_ptr, xcd, counters, plan_ints) of torch.ops.stag.*"""
     if plan_t is None:
         return (None, None, None, None, None, None, [0, 0, 0, 0, 0, 0, 0, 0])
-    key = (tiles, _lib.stream_of(dev))
-    counters = plan_t["counters"].get(key)
-    if counters is None:
-        counters = torch.zeros(max(plan_t["n_long"], 1) * tiles, dtype=torch.int32, device=dev)
-        plan_t["counters"][key] = counters
+    _, counters = _plan_counters(plan_t, tiles, dev)
     order, strides, _ = csrv.xcd_order(plan_t, width, drawn) if width and plan_t.get("xcd_on") else (None, (0, 0), 0)
     ints = [plan_t["seg_len"], plan_t["n_units"], plan_t["n_long"], plan_t["n_seg"], plan_t["n_heavy"], plan_t["n_blocks"],
             *strides]
@@ -1838,11 +1847,8 @@ def _gat_plan_args(csrv, plan_t, dev, gat_width, transposed=False):
     """The plan arguments of torch.ops.stag.gat_fwd / gat_bwd: (units, long_rows, long_seg_ptr, block_ptr, xcd, counters,
     plan_ints), the unit batches the XCD-aware ones when the plan has them (transposed: the second plan of gat_bwd has no
     xcd slot)."""
-    key = (1, _lib.stream_of(dev))
-    counters = plan_t["counters"].get(key)
-    if counters is None:
-        counters = torch.zeros(max(plan_t["n_long"], 1), dtype=torch.int32, device=dev)
-        plan_t["counters"][key] = counters
+    _, counters = _plan_counters(plan_t, 1, dev)    # shared with the aggregation launches of one channel tile: the GAT
+                                                    # kernels use the first n_long ints only
     units, block_ptr, n_blocks, n_heavy = plan_t["units"], plan_t["block_ptr"], plan_t["n_blocks"], plan_t["n_heavy"]
     local = None
     if plan_t.get("xcd_on"):
