@@ -431,12 +431,89 @@ static_assert(kBlkUnits <= 64 && kBlkThreads % 64 == 0 && kBlkThreads <= 1024, "
 #ifndef STAG_GAT_LDS_MIN_BWD
 #define STAG_GAT_LDS_MIN_BWD 32000  // backward passes: 5
 #endif
+
+// ---- half rows in the cooperative forward (stag_gat_fwd_half: DT = STAG_DTYPE_F16 / _BF16 of the kernel below) ------------
+// a.ft points at fp16 / bf16 rows of H*F elements (a.ft_bytes: their extent in bytes when the descriptor reaches all
+// of them); el, er, the in-norm factor, out, stats and the segment states are fp32 as before.  The gather — the one
+// thing this launch waits for — is E x H*F*2 bytes.
+// Rows in flight and workgroups per CU have knobs of their own (the fp32 values were tuned for 1-KB rows): none of
+// them changes a bit of the result.  Round 10, cfg5 on bf16 rows, us per call (tools/ab_bench.py run --gat-half bf16,
+// no noise): rows in flight 1 | 2 | 4 at 4 workgroups per CU 190.3 | 161.7 | 152.8; 4 | 5 | 6 workgroups per CU at 4
+// rows 152.8 | 146.1 | 141.2 (6 needs <= 80 VGPRs: only with 4 merge states per round trip, which a shard-sized launch
+// pays for — not taken).  Half-size rows out of a table that fits the Infinity Cache want MORE in flight, not fewer.
+#ifndef STAG_GAT_HALF_NR
+#define STAG_GAT_HALF_NR STAG_GAT_NR_FWD                 // rows of 2 or 4 chunks per lane, rows out of the Infinity Cache
+#endif
+#ifndef STAG_GAT_HALF_NR_LOCAL
+#define STAG_GAT_HALF_NR_LOCAL STAG_GAT_NR_FWD_LOCAL     // ... XCD-local batches
+#endif
+#ifndef STAG_GAT_HALF_NR_NARROW
+#define STAG_GAT_HALF_NR_NARROW STAG_GAT_NR_FWD_NARROW   // rows of one chunk per lane
+#endif
+#ifndef STAG_GAT_HALF_LDS_MIN
+#define STAG_GAT_HALF_LDS_MIN 32000                      // bytes of LDS asked for at least: 160 KB / this = 5 workgroups per CU
+#endif
+#ifndef STAG_GAT_HALF_MERGE_NF
+// Segment states of a long row fetched per round trip by the row's merge.  The fp32 kernel takes 12 (kGatMergeNF) in 121
+// VGPRs; here 12 come to 143 (3 workgroups per CU instead of 4, and scratch when the allocator is held to 128), 8 to 93.
+// The states are folded in segment order whatever the count: no bit depends on it.
+#define STAG_GAT_HALF_MERGE_NF 8
+#endif
+constexpr int kGatHalfMergeNF = STAG_GAT_HALF_MERGE_NF;
+constexpr int kGatRowF32 = 0;     // DT of fp32 rows: file-local, not a public dtype (stag_gat_fwd_half refuses ft_dtype 0)
+static_assert(kGatRowF32 != STAG_DTYPE_F16 && kGatRowF32 != STAG_DTYPE_BF16, "the fp32 row type is none of the public half types");
+typedef _Float16 gat_f16x2_t __attribute__((ext_vector_type(2)));
+typedef unsigned int gat_u32x2_t __attribute__((ext_vector_type(2)));
+
+// channels [k0, k0 + 4) of row u of ft: one 8-byte load (`buffer_load_dwordx2` behind the descriptor; a global load
+// of 8 bytes past 2^24 rows or 4 GiB) widened exactly — bf16 by a shift / a mask, fp16 by
+// v_cvt_f32_f16 (subnormals included: the conversion is an instruction, not arithmetic under the FP mode)
+template <int DT>
+__device__ __forceinline__ void gat_row4(const GatArgs& a, __amdgpu_buffer_rsrc_t rft, bool ft_buf, int u, int HF, int k0,
+                                         float (&v)[4]) {
+  static_assert(DT == STAG_DTYPE_F16 || DT == STAG_DTYPE_BF16, "half rows: fp16 or bf16");
+  gat_u32x2_t t;
+  if (ft_buf) {
+    t = __builtin_amdgcn_raw_buffer_load_b64(rft, (int)(__umul24((uint32_t)u, (uint32_t)HF * 2u) + (uint32_t)k0 * 2u), 0, 0);
+  } else {
+    const char* p = reinterpret_cast<const char*>(a.ft) + ((int64_t)u * HF + k0) * 2;
+    t = *reinterpret_cast<const gat_u32x2_t*>(p);
+  }
+  const uint32_t wd[2] = {t.x, t.y};
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    if constexpr (DT == STAG_DTYPE_BF16) {
+      v[2 * i] = __uint_as_float(wd[i] << 16);
+      v[2 * i + 1] = __uint_as_float(wd[i] & 0xFFFF0000u);
+    } else {
+      const gat_f16x2_t h = __builtin_bit_cast(gat_f16x2_t, wd[i]);
+      v[2 * i] = (float)h.x;
+      v[2 * i + 1] = (float)h.y;
+    }
+  }
+}
+
 // NRF: rows in flight per team in the gather — STAG_GAT_NR_FWD (1) when the rows come out of the Infinity Cache (cfg5: a
 // 173 MB table, uniformly random sources), STAG_GAT_NR_FWD_LOCAL (2) when the batches are XCD-local (stag_plan_blocks_xcd*:
 // the caller says so by a non-NULL plan->xcd_order) and the rows come out of an XCD's L2, where the gather is bound by
 // latency, not by the fabric (round 4; tools/bench_configs.py --lib, us, 1 | 2 | 4 rows: PPI batch 4 x 256 356.6 | 334.2 |
 // 337.3; cfg5 221.8 | 238.0 | 252.0).
-template <int LPE, int CPL, int NRF = STAG_GAT_NR_FWD>
+// DT: the type of the ft rows — kGatRowF32 (stag_gat_fwd), STAG_DTYPE_F16 / STAG_DTYPE_BF16 (stag_gat_fwd_half).  It picks
+// the row load (bufrow4 / loadrow4, or gat_row4<DT>) and the merge width (kGatMergeNF, or kGatHalfMergeNF) and nothing
+// else: draws, logits, statistics, the fma chain in edge order, the padding of a round and the segment merge are ONE
+// text, so the three agree bit for bit on rows that widen to the same floats.  The STAG_GAT_DBG & 16 trace and
+// STAG_GAT_SGPR_ATTR apply to every DT; both are inert at their defaults (0: no trace code, no attribute).
+// The body stays this __global__ function's own, with GatArgs its by-value parameter, and no part of it lives in a
+// __device__ function, a macro or an included fragment.  This kernel is tuned to the VGPR, and every other way of
+// sharing the text was tried and moved the register allocation (the DT parameter alone leaves all 27 instantiations'
+// assembly and resource lines as they were when fp32 and half rows had a copy each; tools/device_code_diff.py):
+//  - the body as a __device__ __forceinline__ gat_fwd_block_body<...>(a) under thin __global__ wrappers, GatArgs by
+//    reference or by value: 12-15 of the 27 instantiations change — fp32 <64, 4, 2> 145 -> 147-149 VGPRs, fp32 <64, 2, 2>
+//    78 -> 81 VGPRs and 6 -> 5 waves per SIMD, SGPR spills 34-36 -> 37-43;
+//  - blk_prologue / blk_unit_of (the backward's helpers) for the batch prologue: the assembly of all 27 changes, their
+//    resource lines do not;
+//  - a gat_merge_row helper shared with gat_fwd_mc_block_kernel: the VGPR counts of 8 kernels move.
+template <int DT, int LPE, int CPL, int NRF = STAG_GAT_NR_FWD>
 __global__ __launch_bounds__(kBlkThreads) STAG_GAT_SGPR_ATTR void gat_fwd_block_kernel(const GatArgs a) {
   extern __shared__ __align__(16) float lds[];
   const int H = a.H, F = a.F, HF = a.HF;
@@ -593,8 +670,12 @@ __global__ __launch_bounds__(kBlkThreads) STAG_GAT_SGPR_ATTR void gat_fwd_block_
       for (int r = 0; r < NR; ++r) {
 #pragma unroll
         for (int cj = 0; cj < CPL; ++cj) {
-          if (ft_buf) bufrow4(rft, u[r], (uint32_t)HF * 4u, (uint32_t)k0[cj] * 4u, fv[r][cj]);
-          else loadrow4(a.ft + (int64_t)u[r] * HF + k0[cj], k0[cj], HF, true, fv[r][cj]);
+          if constexpr (DT == kGatRowF32) {
+            if (ft_buf) bufrow4(rft, u[r], (uint32_t)HF * 4u, (uint32_t)k0[cj] * 4u, fv[r][cj]);
+            else loadrow4(a.ft + (int64_t)u[r] * HF + k0[cj], k0[cj], HF, true, fv[r][cj]);
+          } else {
+            gat_row4<DT>(a, rft, ft_buf, u[r], HF, k0[cj], fv[r][cj]);
+          }
         }
       }
 #pragma unroll
@@ -616,8 +697,12 @@ __global__ __launch_bounds__(kBlkThreads) STAG_GAT_SGPR_ATTR void gat_fwd_block_
 #pragma unroll
           for (int cj = 0; cj < CPL; ++cj) {
             if (kin[cj]) {
-              if (ft_buf) bufrow4(rft, u, (uint32_t)HF * 4u, (uint32_t)k0[cj] * 4u, fv[r][cj]);
-              else loadrow4(a.ft + (int64_t)u * HF + k0[cj], k0[cj], HF, true, fv[r][cj]);
+              if constexpr (DT == kGatRowF32) {
+                if (ft_buf) bufrow4(rft, u, (uint32_t)HF * 4u, (uint32_t)k0[cj] * 4u, fv[r][cj]);
+                else loadrow4(a.ft + (int64_t)u * HF + k0[cj], k0[cj], HF, true, fv[r][cj]);
+              } else {
+                gat_row4<DT>(a, rft, ft_buf, u, HF, k0[cj], fv[r][cj]);
+              }
             }
           }
         }
@@ -686,11 +771,12 @@ __global__ __launch_bounds__(kBlkThreads) STAG_GAT_SGPR_ATTR void gat_fwd_block_
       float A[4] = {0.f, 0.f, 0.f, 0.f};
       // The merge is a chain on the launch's critical path when the launch is small (a shard of an 8-way partition: the
       // 13k-edge hub's 205 segment states, one L2 round trip each, were 97 of the shard's 145 us).  The states are fetched
-      // kGatMergeNF (12) at a time — independent loads, clamped to the last segment instead of branching — and folded in
-      // segment order as before, so the row's bits do not change.  12 states are 121 VGPRs: free, because the kernel's LDS
-      // request (STAG_GAT_LDS_MIN) caps a SIMD at 4 waves, which registers allow up to 128 (one-GPU cfg5 with 4 | 8 | 12
-      // at a time: 223.8 | 223.5 | 223.1 us; the hub's shard of eight: 70.2 | 57.4 | 53.0 us).
-      constexpr int NFM = CPL == 1 ? kGatMergeNF : 1;     // (wider rows, CPL chunks per lane: their register budget has no room, one state at a time as before)
+      // kGatMergeNF (12; half rows kGatHalfMergeNF, 8) at a time — independent loads, clamped to the last segment instead of
+      // branching — and folded in segment order as before, so the row's bits do not change.  12 states are 121 VGPRs on fp32
+      // rows: free, because the kernel's LDS request (STAG_GAT_LDS_MIN) caps a SIMD at 4 waves, which registers allow up to
+      // 128 (one-GPU cfg5 with 4 | 8 | 12 at a time: 223.8 | 223.5 | 223.1 us; the hub's shard of eight: 70.2 | 57.4 | 53.0 us).
+      // (wider rows, CPL chunks per lane: their register budget has no room, one state at a time as before)
+      constexpr int NFM = CPL == 1 ? (DT == kGatRowF32 ? kGatMergeNF : kGatHalfMergeNF) : 1;
       // the row's maximum per head.  Where the team's lanes are exactly H heads x F/4 lanes (cfg5: 8 x 8 = 64), the F/4
       // lanes of a head take every (F/4)-th segment each and exchange their maxima: 205 states in 4 round trips
       // instead of 26 (a maximum does not care about the order)
@@ -748,369 +834,13 @@ __global__ __launch_bounds__(kBlkThreads) STAG_GAT_SGPR_ATTR void gat_fwd_block_
   GAT_TS(6)
 }
 
-// ---- the cooperative forward on half rows (stag_gat_fwd_half) ---------------------------------------------------------
-// a.ft points at fp16 / bf16 rows of H*F elements (a.ft_bytes: their extent in bytes when the descriptor reaches all
-// of them); el, er, the in-norm factor, out, stats and the segment states are fp32 as before.  The gather — the one
-// thing this launch waits for — is E x H*F*2 bytes.
-// Rows in flight and workgroups per CU have knobs of their own (the fp32 values were tuned for 1-KB rows): none of
-// them changes a bit of the result.  Round 10, cfg5 on bf16 rows, us per call (tools/ab_bench.py run --gat-half bf16,
-// no noise): rows in flight 1 | 2 | 4 at 4 workgroups per CU 190.3 | 161.7 | 152.8; 4 | 5 | 6 workgroups per CU at 4
-// rows 152.8 | 146.1 | 141.2 (6 needs <= 80 VGPRs: only with 4 merge states per round trip, which a shard-sized launch
-// pays for — not taken).  Half-size rows out of a table that fits the Infinity Cache want MORE in flight, not fewer.
-#ifndef STAG_GAT_HALF_NR
-#define STAG_GAT_HALF_NR STAG_GAT_NR_FWD                 // rows of 2 or 4 chunks per lane, rows out of the Infinity Cache
-#endif
-#ifndef STAG_GAT_HALF_NR_LOCAL
-#define STAG_GAT_HALF_NR_LOCAL STAG_GAT_NR_FWD_LOCAL     // ... XCD-local batches
-#endif
-#ifndef STAG_GAT_HALF_NR_NARROW
-#define STAG_GAT_HALF_NR_NARROW STAG_GAT_NR_FWD_NARROW   // rows of one chunk per lane
-#endif
-#ifndef STAG_GAT_HALF_LDS_MIN
-#define STAG_GAT_HALF_LDS_MIN 32000                      // bytes of LDS asked for at least: 160 KB / this = 5 workgroups per CU
-#endif
-#ifndef STAG_GAT_HALF_MERGE_NF
-// Segment states of a long row fetched per round trip by the row's merge.  The fp32 kernel takes 12 (kGatMergeNF) in 121
-// VGPRs; here 12 come to 143 (3 workgroups per CU instead of 4, and scratch when the allocator is held to 128), 8 to 93.
-// The states are folded in segment order whatever the count: no bit depends on it.
-#define STAG_GAT_HALF_MERGE_NF 8
-#endif
-constexpr int kGatHalfMergeNF = STAG_GAT_HALF_MERGE_NF;
-typedef _Float16 gat_f16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned int gat_u32x2_t __attribute__((ext_vector_type(2)));
-
-// channels [k0, k0 + 4) of row u of ft: one 8-byte load (`buffer_load_dwordx2` behind the descriptor; a global load
-// of 8 bytes past 2^24 rows or 4 GiB) widened exactly — bf16 by a shift / a mask, fp16 by
-// v_cvt_f32_f16 (subnormals included: the conversion is an instruction, not arithmetic under the FP mode)
-template <int DT>
-__device__ __forceinline__ void gat_row4(const GatArgs& a, __amdgpu_buffer_rsrc_t rft, bool ft_buf, int u, int HF, int k0,
-                                         float (&v)[4]) {
-  static_assert(DT == STAG_DTYPE_F16 || DT == STAG_DTYPE_BF16, "half rows: fp16 or bf16");
-  gat_u32x2_t t;
-  if (ft_buf) {
-    t = __builtin_amdgcn_raw_buffer_load_b64(rft, (int)(__umul24((uint32_t)u, (uint32_t)HF * 2u) + (uint32_t)k0 * 2u), 0, 0);
-  } else {
-    const char* p = reinterpret_cast<const char*>(a.ft) + ((int64_t)u * HF + k0) * 2;
-    t = *reinterpret_cast<const gat_u32x2_t*>(p);
-  }
-  const uint32_t wd[2] = {t.x, t.y};
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    if constexpr (DT == STAG_DTYPE_BF16) {
-      v[2 * i] = __uint_as_float(wd[i] << 16);
-      v[2 * i + 1] = __uint_as_float(wd[i] & 0xFFFF0000u);
-    } else {
-      const gat_f16x2_t h = __builtin_bit_cast(gat_f16x2_t, wd[i]);
-      v[2 * i] = (float)h.x;
-      v[2 * i + 1] = (float)h.y;
-    }
-  }
-}
-
-// gat_fwd_block_kernel<LPE, CPL, NRF> with gat_row4 as its row load and nothing else changed (that kernel is tuned to
-// the VGPR and stays as it is; the debug trace is left out): draws, logits, statistics, the fma chain in edge order, the
-// padding of a round and the segment merge are the same text, so the two agree bit for bit on rows that widen to the
-// same floats.
-template <int DT, int LPE, int CPL, int NRF>
-__global__ __launch_bounds__(kBlkThreads) void gat_fwd_half_block_kernel(const GatArgs a) {
-  extern __shared__ __align__(16) float lds[];
-  const int H = a.H, F = a.F, HF = a.HF;
-  float* s_w = lds;                                   // [kBlkEdges][H] logits, then p = exp(e - m)
-  float* s_m = s_w + kBlkEdges * H;                   // [kBlkUnits][H]
-  float* s_l = s_m + kBlkUnits * H;                   // [kBlkUnits][H]
-  int* s_u = reinterpret_cast<int*>(s_l + kBlkUnits * H);   // [kBlkEdges] source row of each edge
-  int* s_start = s_u + kBlkEdges;                     // [kBlkUnits + 1] first edge slot of each unit
-  int4* s_unit = reinterpret_cast<int4*>(s_start + kBlkUnits + 4);   // [kBlkUnits] (row, start, len, slot); 16-B aligned
-  const int t = threadIdx.x;
-  const int ub = a.block_ptr[blockIdx.x], nu = a.block_ptr[blockIdx.x + 1] - ub;
-
-  // ---- the batch: unit records, edge-slot prefix -----------------------------------------------
-  if (t < kBlkUnits) {
-    int4 q = make_int4(0, 0, 0, -1);
-    if (t < nu) q = *reinterpret_cast<const int4*>(a.units + ub + t);
-    s_unit[t] = q;
-    int incl = q.z;                                    // inclusive scan of the lengths over lanes 0..31
-#pragma unroll
-    for (int d = 1; d < kBlkUnits; d <<= 1) {
-      const int up = __shfl_up(incl, d, kBlkUnits);          // lanes 0..kBlkUnits-1 of wave 0
-      if (t >= d) incl += up;
-    }
-    s_start[t + 1] = incl;
-    if (t == 0) s_start[0] = 0;
-  }
-  __syncthreads();
-  const int ne = s_start[nu];                          // edges of the batch (<= kBlkEdges by the plan)
-
-  // ---- phase 1: thread t <-> edge slot t ---------------------------------------------------------
-  uint32_t kmask = 0;                                  // attention dropout: bit h = head h of my edge survives
-  if (t < ne) {
-    int lo = 0, hi = nu;                               // unit j with s_start[j] <= t < s_start[j+1]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (s_start[mid] <= t) lo = mid; else hi = mid;
-    }
-    const int4 q = s_unit[lo];
-    const int row = (q.w >= 0) ? a.long_rows[q.x] : q.x;
-    const int p = q.y + (t - s_start[lo]);
-    const int u = a.indices[p];
-    s_u[t] = u;
-    const int64_t ed = a.eid ? a.eid[p] : p;
-    const uint32_t n = a.pos_lo + (a.nidx ? (uint32_t)a.nidx[p] : (uint32_t)p);
-    const PhiloxKey key = resolve_epoch(a.key);
-    const int nchunk = (H + 3) / 4;
-    const bool h4 = (H & 3) == 0 && a.hvec;           // el / er / nscale rows as dwordx4 (one L1 lookup per 4 heads)
-    for (int cc = 0; cc < nchunk; ++cc) {
-      float w[4], sl4[4], sr4[4], ns4[4] = {1.f, 1.f, 1.f, 1.f};
-      if (h4) {
-        load4(a.el + (int64_t)u * H, 4 * cc, H, true, sl4);
-        load4(a.er + (int64_t)row * H, 4 * cc, H, true, sr4);
-        if (a.nscale) load4(a.nscale + (int64_t)row * H, 4 * cc, H, true, ns4);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int h = 4 * cc + j;
-          sl4[j] = h < H ? a.el[(int64_t)u * H + h] : 0.f;
-          sr4[j] = h < H ? a.er[(int64_t)row * H + h] : 0.f;
-          if (a.nscale && h < H) ns4[j] = a.nscale[(int64_t)row * H + h];
-        }
-      }
-      head_w4(a, key, n, ed, (uint32_t)cc, w);
-      if (a.drop_keep > 0.f) kmask |= drop_keep4(a, resolve_epoch(a.drop_key), n, (uint32_t)cc) << (4 * cc);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int h = 4 * cc + j;
-        if (h < H) {
-          const float sL = sl4[j] + sr4[j];
-          const float lr = sL > 0.f ? sL : a.neg_slope * sL;
-          s_w[t * H + h] = (w[j] * ns4[j]) * lr;
-        }
-      }
-    }
-  }
-  __syncthreads();
-
-  // ---- phase 1b: thread <-> (unit, head): softmax statistics, logits -> p ---------------------------
-  for (int i = t; i < nu * H; i += kBlkThreads) {
-    const int j = i / H, h = i - j * H;
-    const int e0 = s_start[j], e1 = s_start[j + 1];
-    float m = -INFINITY;
-    for (int e = e0; e < e1; ++e) m = fmaxf(m, s_w[e * H + h]);
-    float l = 0.f;
-    for (int e = e0; e < e1; ++e) {
-      const float pe = __expf(s_w[e * H + h] - m);
-      s_w[e * H + h] = pe;
-      l += pe;
-    }
-    s_m[i] = m;
-    s_l[i] = l;
-  }
-  __syncthreads();
-  if (a.drop_keep > 0.f) {       // (uniform) the softmax statistics saw every edge; the weighted sum sees the survivors
-    if (t < ne) {
-      for (int h = 0; h < H; ++h)
-        s_w[t * H + h] = ((kmask >> h) & 1u) ? s_w[t * H + h] * a.drop_scale : 0.f;
-    }
-    __syncthreads();
-  }
-
-  // ---- phase 2: a team per unit, weighted gather -------------------------------------------------------
-  // lane c owns CPL chunks of 4 channels: [4 (c + LPE j), +4), j < CPL  (H*F <= 256: one; up to 1024: 2 or 4)
-  constexpr int TEAMS = kBlkThreads / LPE, NR = STAG_GAT_BRANCHFREE ? NRF : (CPL >= 4 ? 2 : STAG_GAT_NR);
-  const int team = t / LPE, c = t % LPE;
-  const int team_lane0 = (int)(t & 63) - c;
-  int k0[CPL], hl[CPL];
-  bool kin[CPL];
-#pragma unroll
-  for (int cj = 0; cj < CPL; ++cj) {
-    lane_chunk(c + LPE * cj, H, F, a.lphp, k0[cj], kin[cj], hl[cj]);
-  }
-  const __amdgpu_buffer_rsrc_t rft =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.ft), 0, (int)a.ft_bytes, 0x00020000);
-  const bool ft_buf = a.ft_bytes != 0;
-  for (int j = team; j < nu; j += TEAMS) {
-    const int4 q = s_unit[j];
-    const int e0 = s_start[j], e1 = s_start[j + 1];
-    float acc[CPL][4];
-#pragma unroll
-    for (int cj = 0; cj < CPL; ++cj) acc[cj][0] = acc[cj][1] = acc[cj][2] = acc[cj][3] = 0.f;
-#if STAG_GAT_BRANCHFREE
-    // The NR gathers of a round are issued back to back with NO control flow between them: a round's source ids and
-    // weights come out of LDS first (positions past the unit's end are clamped to its last edge and carry weight 0:
-    // a repeated row, which the L1 serves), lanes without a chunk load chunk 0 and store nothing.  With the
-    // `if (e + r < e1)` / `if (kin)` branches around each load the compiler could not count the loads in flight and put
-    // `s_waitcnt vmcnt(0)` in front of every next LDS read: the "NR rows in flight" went out one at a time.
-    for (int e = e0; e < e1; e += NR) {
-      float fv[NR][CPL][4], pe[NR][CPL];
-      int u[NR];
-#pragma unroll
-      for (int r = 0; r < NR; ++r) {
-        const int er = min(e + r, e1 - 1);
-        u[r] = s_u[er];
-#pragma unroll
-        for (int cj = 0; cj < CPL; ++cj) {
-          const float wv = s_w[er * H + (kin[cj] ? hl[cj] : 0)];
-          pe[r][cj] = (e + r < e1) ? wv : 0.f;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < NR; ++r) {
-#pragma unroll
-        for (int cj = 0; cj < CPL; ++cj) gat_row4<DT>(a, rft, ft_buf, u[r], HF, k0[cj], fv[r][cj]);
-      }
-#pragma unroll
-      for (int r = 0; r < NR; ++r) {
-#pragma unroll
-        for (int cj = 0; cj < CPL; ++cj) {
-#pragma unroll
-          for (int x = 0; x < 4; ++x) acc[cj][x] = __builtin_fmaf(pe[r][cj], fv[r][cj][x], acc[cj][x]);
-        }
-      }
-    }
-#else
-    for (int e = e0; e < e1; e += NR) {
-      float fv[NR][CPL][4];
-#pragma unroll
-      for (int r = 0; r < NR; ++r) {
-        if (e + r < e1) {
-          const int u = s_u[e + r];
-#pragma unroll
-          for (int cj = 0; cj < CPL; ++cj) {
-            if (kin[cj]) gat_row4<DT>(a, rft, ft_buf, u, HF, k0[cj], fv[r][cj]);
-          }
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < NR; ++r) {
-        if (e + r < e1) {
-#pragma unroll
-          for (int cj = 0; cj < CPL; ++cj) {
-            if (kin[cj]) {
-              const float pe = s_w[(e + r) * H + hl[cj]];
-#pragma unroll
-              for (int x = 0; x < 4; ++x) acc[cj][x] = __builtin_fmaf(pe, fv[r][cj][x], acc[cj][x]);
-            }
-          }
-        }
-      }
-    }
-#endif
-    if (q.w < 0) {
-      // ---- whole row: normalise and store --------------------------------------------------------
-#pragma unroll
-      for (int cj = 0; cj < CPL; ++cj) {
-        if (!kin[cj]) continue;
-        const float m = s_m[j * H + hl[cj]], l = s_l[j * H + hl[cj]];
-        const float inv = (l > 0.f) ? 1.0f / l : 0.f;
-        float o[4];
-#pragma unroll
-        for (int x = 0; x < 4; ++x) o[x] = acc[cj][x] * inv;
-        store4_out(a.out + (int64_t)q.x * HF, k0[cj], HF, true, o);
-        if (a.stats && k0[cj] % F == 0) {
-          a.stats[(int64_t)q.x * 2 * H + hl[cj]] = m;
-          a.stats[(int64_t)q.x * 2 * H + H + hl[cj]] = l;
-        }
-      }
-      continue;
-    }
-    // ---- segment: publish (acc, m, l) write-through, take a ticket; the last arriver merges ----------
-    const int v = q.x, slot = q.w, row = a.long_rows[v];
-    const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(a.ws, 0, (int)a.ws_bytes, 0x00020000);
-    const uint32_t base = (uint32_t)slot * ((uint32_t)a.ws_stride * 4u);
-#pragma unroll
-    for (int cj = 0; cj < CPL; ++cj) {
-      if (!kin[cj]) continue;
-      store4_sc1(rws, base + (uint32_t)k0[cj] * 4u, k0[cj], HF, true, acc[cj]);
-      if (k0[cj] % F == 0) {
-        const float m = s_m[j * H + hl[cj]], l = s_l[j * H + hl[cj]];
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(m), rws, (int)(base + (uint32_t)(HF + hl[cj]) * 4u), 0, 16);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(l), rws, (int)(base + (uint32_t)(HF + H + hl[cj]) * 4u), 0, 16);
-      }
-    }
-    const int s0 = a.long_seg_ptr[v], s1 = a.long_seg_ptr[v + 1];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int ticket = 0;
-    if (c == 0)
-      ticket = __hip_atomic_fetch_add(a.seg_counters + v, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ticket = __builtin_amdgcn_ds_bpermute(team_lane0 << 2, ticket);
-    if (ticket != (s1 - s0) - 1) continue;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (c == 0) a.seg_counters[v] = 0;
-#pragma unroll
-    for (int cj = 0; cj < CPL; ++cj) {
-      if (!kin[cj]) continue;
-      float M = -INFINITY, L = 0.f;
-      float A[4] = {0.f, 0.f, 0.f, 0.f};
-      // The merge is a chain on the launch's critical path when the launch is small (a shard of an 8-way partition: the
-      // 13k-edge hub's 205 segment states, one L2 round trip each, were 97 of the shard's 145 us).  The states are fetched
-      // kGatHalfMergeNF (8) at a time — independent loads, clamped to the last segment instead of branching — and folded in
-      // segment order as before, so the row's bits do not change.  12 states are 121 VGPRs: free, because the kernel's LDS
-      // request (STAG_GAT_LDS_MIN) caps a SIMD at 4 waves, which registers allow up to 128 (one-GPU cfg5 with 4 | 8 | 12
-      // at a time: 223.8 | 223.5 | 223.1 us; the hub's shard of eight: 70.2 | 57.4 | 53.0 us).
-      constexpr int NFM = CPL == 1 ? kGatHalfMergeNF : 1;     // (wider rows, CPL chunks per lane: their register budget has no room, one state at a time as before)
-      // the row's maximum per head.  Where the team's lanes are exactly H heads x F/4 lanes (cfg5: 8 x 8 = 64), the F/4
-      // lanes of a head take every (F/4)-th segment each and exchange their maxima: 205 states in 4 round trips
-      // instead of 26 (a maximum does not care about the order)
-      const int lph = a.lphp;
-      if (CPL == 1 && lph >= 2 && lph * 4 == F && H * lph == LPE) {
-        const int g = c & (lph - 1);
-        for (int sg = s0 + g; sg < s1; sg += 2 * NFM * lph) {
-          float mm[2 * NFM];
-#pragma unroll
-          for (int i = 0; i < 2 * NFM; ++i)
-            mm[i] = a.ws[(int64_t)min(sg + i * lph, s1 - 1) * a.ws_stride + HF + hl[cj]];
-#pragma unroll
-          for (int i = 0; i < 2 * NFM; ++i) M = fmaxf(M, mm[i]);
-        }
-        for (int d = 1; d < lph; d <<= 1) M = fmaxf(M, __shfl_xor(M, d));
-      } else {
-        for (int sg = s0; sg < s1; sg += 2 * NFM) {
-          float mm[2 * NFM];
-#pragma unroll
-          for (int i = 0; i < 2 * NFM; ++i)
-            mm[i] = a.ws[(int64_t)min(sg + i, s1 - 1) * a.ws_stride + HF + hl[cj]];
-#pragma unroll
-          for (int i = 0; i < 2 * NFM; ++i) M = fmaxf(M, mm[i]);
-        }
-      }
-      for (int sg = s0; sg < s1; sg += NFM) {
-        float tt[NFM][4], ms[NFM], ls[NFM];
-#pragma unroll
-        for (int i = 0; i < NFM; ++i) {
-          const float* wr = a.ws + (int64_t)min(sg + i, s1 - 1) * a.ws_stride;
-          load4(wr, k0[cj], HF, true, tt[i]);
-          ms[i] = wr[HF + hl[cj]];
-          ls[i] = wr[HF + H + hl[cj]];
-        }
-#pragma unroll
-        for (int i = 0; i < NFM; ++i) {
-          if (sg + i < s1) {
-            const float sc = __expf(ms[i] - M);
-            L += ls[i] * sc;
-#pragma unroll
-            for (int x = 0; x < 4; ++x) A[x] = __builtin_fmaf(tt[i][x], sc, A[x]);
-          }
-        }
-      }
-      const float inv = (L > 0.f) ? 1.0f / L : 0.f;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) A[x] *= inv;
-      store4_out(a.out + (int64_t)row * HF, k0[cj], HF, true, A);
-      if (a.stats && k0[cj] % F == 0) {
-        a.stats[(int64_t)row * 2 * H + hl[cj]] = M;
-        a.stats[(int64_t)row * 2 * H + H + hl[cj]] = L;
-      }
-    }
-  }
-}
-
 // ---- Monte-Carlo form of the cooperative forward (stag_gat_fwd_mc) -------------------------------------------------
 // The reference's models average S noisy passes (stag/models.py:45-55, :67-68); on a first layer every pass gathers the
-// same ft rows and only the H-wide draws differ.  gat_fwd_mc_block_kernel is gat_fwd_block_kernel carrying `ns` <= SP
+// same ft rows and only the H-wide draws differ.  gat_fwd_mc_block_kernel is gat_fwd_block_kernel<kGatRowF32, ...> carrying `ns` <= SP
 // samples per launch: phase 1 draws the H weights of every sample from one load of el / er / the source id (sample s
 // at the key advanced by s * stride), phase 1b forms each sample's softmax statistics, phase 2 gathers each row ONCE
 // and folds it into SP accumulator sets.  Per sample the arithmetic, its order and the padding of a round are those of
-// gat_fwd_block_kernel<LPE, CPL, NRF> — sample s is the single-sample launch at offset + s * stride, bit for bit.
+// gat_fwd_block_kernel<kGatRowF32, LPE, CPL, NRF> — sample s is the single-sample launch at offset + s * stride, bit for bit.
 // LDS: ns x (256 H + 64 H) floats of logits and statistics + the batch records, padded to STAG_GAT_LDS_MIN as the
 // single-sample kernel is.  Segment states: [slot][wsp][ws_stride], one ticket per segment for all its samples; the last
 // arriver merges sample by sample (the merge's registers are the single-sample kernel's, not SP times them).
@@ -1340,7 +1070,8 @@ __global__ __launch_bounds__(kBlkThreads) void gat_fwd_mc_block_kernel(const Gat
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (c == 0) a.seg_counters[v] = 0;
-    // the merge of gat_fwd_block_kernel, one sample at a time: segment sg of sample s is state sg * wsp + s
+    // the merge of gat_fwd_block_kernel<kGatRowF32, LPE, CPL, NRF> (fp32 rows: kGatMergeNF states per round trip), one sample
+    // at a time: segment sg of sample s is state sg * wsp + s
 #pragma unroll 1
     for (int s = 0; s < ns; ++s) {
       const float* ws = a.ws + (int64_t)s * a.ws_stride;
@@ -2304,16 +2035,22 @@ extern "C" size_t stag_gat_workspace_bytes(int32_t n_seg, int32_t H, int32_t F) 
   return (size_t)n_seg * (size_t)((H * F + 2 * H + 3) & ~3) * sizeof(float);   // rows padded to 16 bytes
 }
 
-extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const float* el,
-                            const float* er, const float* ft, int32_t H, int32_t F, float neg_slope,
-                            const stag_noise_spec* spec, const float* norm_scale, const stag_gat_drop* drop,
-                            float* out, float* stats_out, void* stream) {
+// ---- the forward entries: stag_gat_fwd, stag_gat_fwd_half, stag_gat_fwd_mc -------------------------------------------
+constexpr int kGatGo = 1;   // gat_fwd_begin: no return code, the entry goes on
+// What stag_gat_fwd and stag_gat_fwd_half check and fill alike, in the order that gives both their return codes, up to
+// the extent of ft (rows of ft_esize-byte elements).  ft_type_ok: the half entry's ft_dtype check, at its place among
+// the others.  Returns kGatGo, or what the entry returns (STAG_OK: a graph without rows).
+static int gat_fwd_begin(GatArgs& a, const stag_csr* csr, const float* el, const float* er, const void* ft,
+                         uint32_t ft_esize, bool ft_type_ok, int32_t H, int32_t F, float neg_slope,
+                         const stag_noise_spec* spec, const float* norm_scale, const stag_gat_drop* drop, float* out,
+                         float* stats_out) {
   if (check_csr_header(csr)) return STAG_EINVAL;
   if (!spec || spec->kind < STAG_NOISE_NONE || spec->kind > STAG_NOISE_BERNOULLI) return STAG_EINVAL;
   if (!out || H <= 0 || F <= 0) return STAG_EINVAL;
+  if (!ft_type_ok) return STAG_EINVAL;
   const int64_t HF64 = (int64_t)H * F;
   // one team spans the H*F row: 256 channels on the one-unit-per-team kernel, 1024 (4 chunks per lane) on the
-  // workgroup-cooperative one (which also wants H <= 16, F % 4 == 0 and a block plan: checked below)
+  // workgroup-cooperative one (which also wants H <= 16, F % 4 == 0 and a block plan: checked by the entry)
   if (H > 64 || HF64 > 1024) return STAG_ENOSYS;
   if (spec->chunk_base != 0) return STAG_ENOSYS;  // heads are not channel-sharded
   if (spec->in_norm && !norm_scale) return STAG_EINVAL;   // the caller runs the row-sum pass first
@@ -2323,34 +2060,93 @@ extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const fl
   if (spec->kind >= STAG_NOISE_NORMAL && spec->param_mode != STAG_PARAM_SCALAR && csr->n_edges > 0 &&
       (!spec->p0 || (spec->kind != STAG_NOISE_BERNOULLI && !spec->p1)))
     return STAG_EINVAL;
-  const int HF = (int)HF64;
-
-  GatArgs a{};
   if (spec->deriv != 0) return STAG_EINVAL;
   fill_gat_args(a, csr, el, er, H, neg_slope, spec, norm_scale);
-  a.ft = ft; a.F = F; a.HF = HF;
+  a.ft = static_cast<const float*>(ft);     // (half rows: gat_row4<DT> reads them as what they are)
+  a.F = F; a.HF = (int)HF64;
   const int prc = check_positions(spec, csr->n_edges, H, spec->kind >= STAG_NOISE_NORMAL || drop_on(drop));
   if (prc) return prc;
   a.out = out; a.stats = stats_out;
   if (fill_drop(a, drop)) return STAG_EINVAL;
-  const uint64_t ftb = (uint64_t)csr->n_src * (uint64_t)HF * 4u;
+  const uint64_t ftb = (uint64_t)csr->n_src * (uint64_t)a.HF * ft_esize;
   a.ft_bytes = (ftb < (1ull << 32) && csr->n_src < (1 << 24)) ? (uint32_t)ftb : 0u;
+  return kGatGo;
+}
 
+// the plan of a forward launch, which may be absent: checked, its units and, where it has segments, their states
+static int gat_fwd_plan(GatArgs& a, const stag_csr* csr, const stag_plan* plan) {
   const bool use_plan = plan_in_use(plan);
-  const size_t need = use_plan ? stag_gat_workspace_bytes(plan->n_seg, H, F) : 0;
+  const size_t need = use_plan ? stag_gat_workspace_bytes(plan->n_seg, a.H, a.F) : 0;
   const int plrc = check_plan(plan, kGatFwdPlan, need);
   if (plrc) return plrc;
   fill_plan(a, csr, plan);
   if (use_plan && plan->n_seg > 0) {
     a.seg_counters = plan->seg_counters; a.n_seg = plan->n_seg;
-    a.ws_stride = (HF + 2 * H + 3) & ~3; a.ws_bytes = (uint32_t)need;
+    a.ws_stride = (a.HF + 2 * a.H + 3) & ~3; a.ws_bytes = (uint32_t)need;
   }
+  return STAG_OK;
+}
+
+// The workgroup-cooperative form of a launch (batches of units: stag_plan_blocks with STAG_BLOCK_EDGES / _UNITS): the
+// fields only it reads, and what picks its kernel.  A head takes lphp lanes, a row H * lphp: lpe lanes per unit with cpl
+// chunks of 4 channels each.  local: the batches are XCD-local, the rows come out of an L2.
+struct GatBlkShape { int lpe, cpl; bool local; };
+static GatBlkShape gat_blk_shape(GatArgs& a, const stag_plan* plan, int lphp) {
+  a.block_ptr = plan->block_ptr;
+  a.lphp = lphp;
+  a.hvec = aligned16(a.el) && aligned16(a.er) && (!a.nscale || aligned16(a.nscale));
+  const int nchunk = a.H * lphp;
+  return {lanes_for(nchunk, 4), nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4), plan->xcd_order != nullptr};
+}
+// bytes of LDS of a workgroup that carries ns samples: logits and statistics per sample + the batch records, at least `floor`
+static size_t gat_blk_lds(int H, int ns, size_t floor) {
+  const size_t lds = (size_t)ns * (kBlkEdges * H + 2 * kBlkUnits * H) * sizeof(float) +
+                     (size_t)(kBlkEdges + kBlkUnits + 4) * sizeof(int) + (size_t)kBlkUnits * sizeof(int4);
+  return lds < floor ? floor : lds;
+}
+
+// The instantiation of a cooperative forward kernel for a shape: launch(LPE, CPL, rows) with std::integral_constants,
+// rows the class of rows in flight, which each entry maps to a knob of its own — rows of one chunk per lane (at most
+// 256 floats) are kGatRowsNarrow whatever the launch; wider ones are kGatRowsWide, or kGatRowsWideLocal on XCD-local
+// batches.  stag_gat_fwd_mc goes through the same ladder as stag_gat_fwd: the same rounds, so the same bits per sample.
+enum { kGatRowsWide, kGatRowsWideLocal, kGatRowsNarrow };
+constexpr int gat_rows(int rows, int wide, int wide_local, int narrow) {
+  return rows == kGatRowsWide ? wide : (rows == kGatRowsWideLocal ? wide_local : narrow);
+}
+template <int V> using gat_int = std::integral_constant<int, V>;
+template <class Launch>
+static void gat_fwd_dispatch(const GatBlkShape& sh, const Launch& launch) {
+  const gat_int<64> w;
+  const gat_int<kGatRowsNarrow> narrow;
+  if (sh.cpl == 4 && sh.local) launch(w, gat_int<4>{}, gat_int<kGatRowsWideLocal>{});
+  else if (sh.cpl == 4) launch(w, gat_int<4>{}, gat_int<kGatRowsWide>{});
+  else if (sh.cpl == 2 && sh.local) launch(w, gat_int<2>{}, gat_int<kGatRowsWideLocal>{});
+  else if (sh.cpl == 2) launch(w, gat_int<2>{}, gat_int<kGatRowsWide>{});
+  else switch (sh.lpe) {
+    case 64: launch(w, gat_int<1>{}, narrow); break;
+    case 32: launch(gat_int<32>{}, gat_int<1>{}, narrow); break;
+    case 16: launch(gat_int<16>{}, gat_int<1>{}, narrow); break;
+    case 8: launch(gat_int<8>{}, gat_int<1>{}, narrow); break;
+    default: launch(gat_int<4>{}, gat_int<1>{}, narrow); break;
+  }
+}
+
+extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const float* el,
+                            const float* er, const float* ft, int32_t H, int32_t F, float neg_slope,
+                            const stag_noise_spec* spec, const float* norm_scale, const stag_gat_drop* drop,
+                            float* out, float* stats_out, void* stream) {
+  GatArgs a{};
+  const int rc = gat_fwd_begin(a, csr, el, er, ft, 4u, true, H, F, neg_slope, spec, norm_scale, drop, out, stats_out);
+  if (rc != kGatGo) return rc;
+  const int HF = a.HF;
+  const bool use_plan = plan_in_use(plan);
+  const int plrc = gat_fwd_plan(a, csr, plan);
+  if (plrc) return plrc;
   bool vec = (F % 4 == 0) && aligned16(ft) && aligned16(out);
   if (a.ws) vec = vec && aligned16(a.ws) && (a.ws_stride % 4 == 0);
 
-  int nchunk = (HF + 3) / 4;
-  int lpe = lanes_for(nchunk, 4);
-  int cpl = nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4);   // chunks of 4 channels per lane
+  const int nchunk = (HF + 3) / 4;
+  const int lpe = lanes_for(nchunk, 4);
   const int tpb = 256 / lpe;
   const dim3 grid((a.n_units + tpb - 1) / tpb);
   const size_t lds_bytes = (size_t)256 * H * sizeof(float);   // [teams][LPE][H]
@@ -2364,37 +2160,14 @@ extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const fl
   if (a.drop_keep > 0.f && !blk_ok) return STAG_ENOSYS;      // attention dropout lives in the cooperative kernels
   if (check_csr(csr)) return STAG_EINVAL;
   if (blk_ok) {
-    // workgroup-cooperative form: batches of units (stag_plan_blocks with STAG_BLOCK_EDGES / _UNITS)
-    a.block_ptr = plan->block_ptr;
-    a.lphp = lphp;
-    nchunk = H * lphp;
-    lpe = lanes_for(nchunk, 4);
-    cpl = nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4);
-    a.hvec = aligned16(el) && aligned16(er) && (!a.nscale || aligned16(a.nscale));
-    size_t lds_blk = (size_t)(kBlkEdges * H + 2 * kBlkUnits * H) * sizeof(float) +
-                     (size_t)(kBlkEdges + kBlkUnits + 4) * sizeof(int) + (size_t)kBlkUnits * sizeof(int4);
-    if (lds_blk < STAG_GAT_LDS_MIN) lds_blk = STAG_GAT_LDS_MIN;
+    const GatBlkShape sh = gat_blk_shape(a, plan, lphp);
+    const size_t lds_blk = gat_blk_lds(H, 1, STAG_GAT_LDS_MIN);
     const dim3 gb(plan->n_blocks);
-    const bool local = plan->xcd_order != nullptr;      // the batches are XCD-local: the rows come out of an L2
-    // rows of at most 256 floats (one chunk per lane): STAG_GAT_NR_FWD_NARROW rows in flight, whatever the launch
-#define STAG_BLK_LAUNCH1(L) \
-  hipLaunchKernelGGL((gat_fwd_block_kernel<L, 1, STAG_GAT_NR_FWD_NARROW>), gb, dim3(kBlkThreads), lds_blk, s, a)
-#define STAG_BLK_LAUNCHW(Cc)                                                                                             \
-  do {                                                                                                                   \
-    if (local) hipLaunchKernelGGL((gat_fwd_block_kernel<64, Cc, STAG_GAT_NR_FWD_LOCAL>), gb, dim3(kBlkThreads), lds_blk, s, a); \
-    else       hipLaunchKernelGGL((gat_fwd_block_kernel<64, Cc>), gb, dim3(kBlkThreads), lds_blk, s, a);                 \
-  } while (0)
-    if (cpl == 4) STAG_BLK_LAUNCHW(4);
-    else if (cpl == 2) STAG_BLK_LAUNCHW(2);
-    else switch (lpe) {
-      case 64: STAG_BLK_LAUNCH1(64); break;
-      case 32: STAG_BLK_LAUNCH1(32); break;
-      case 16: STAG_BLK_LAUNCH1(16); break;
-      case 8: STAG_BLK_LAUNCH1(8); break;
-      default: STAG_BLK_LAUNCH1(4); break;
-    }
-#undef STAG_BLK_LAUNCH1
-#undef STAG_BLK_LAUNCHW
+    gat_fwd_dispatch(sh, [&](auto L, auto Cc, auto rows) {
+      constexpr int NRF = gat_rows(decltype(rows)::value, STAG_GAT_NR_FWD, STAG_GAT_NR_FWD_LOCAL, STAG_GAT_NR_FWD_NARROW);
+      hipLaunchKernelGGL((gat_fwd_block_kernel<kGatRowF32, decltype(L)::value, decltype(Cc)::value, NRF>), gb,
+                         dim3(kBlkThreads), lds_blk, s, a);
+    });
     return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
   }
 #define STAG_GAT_LAUNCH(L)                                                                         \
@@ -2413,91 +2186,40 @@ extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const fl
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
-// stag_gat_fwd on fp16 / bf16 ft rows, the workgroup-cooperative form only (gat_fwd_half_block_kernel).  The checks
+// stag_gat_fwd on fp16 / bf16 ft rows, the workgroup-cooperative form only (gat_fwd_block_kernel<DT, ...>).  The checks
 // run in stag_gat_fwd's order; what that entry would hand to gat_fwd_kernel is STAG_ENOSYS here (the caller widens ft
 // and calls stag_gat_fwd).  Every refusal comes before any device work.
 extern "C" int stag_gat_fwd_half(const stag_csr* csr, const stag_plan* plan, const float* el, const float* er,
                                  const void* ft, int32_t ft_dtype, int32_t H, int32_t F, float neg_slope,
                                  const stag_noise_spec* spec, const float* norm_scale, const stag_gat_drop* drop,
                                  float* out, float* stats_out, void* stream) {
-  if (check_csr_header(csr)) return STAG_EINVAL;
-  if (!spec || spec->kind < STAG_NOISE_NONE || spec->kind > STAG_NOISE_BERNOULLI) return STAG_EINVAL;
-  if (!out || H <= 0 || F <= 0) return STAG_EINVAL;
-  if (ft_dtype != STAG_DTYPE_F16 && ft_dtype != STAG_DTYPE_BF16) return STAG_EINVAL;
-  const int64_t HF64 = (int64_t)H * F;
-  if (H > 64 || HF64 > 1024) return STAG_ENOSYS;
-  if (spec->chunk_base != 0) return STAG_ENOSYS;  // heads are not channel-sharded
-  if (spec->in_norm && !norm_scale) return STAG_EINVAL;   // the caller runs the row-sum pass first
-  if (csr->n_dst == 0) return STAG_OK;
-  if (csr->n_edges > 0 && (!csr->indices || !el || !er || !ft)) return STAG_EINVAL;
-  if (spec->kind == STAG_NOISE_EXPLICIT && !spec->p0 && csr->n_edges > 0) return STAG_EINVAL;
-  if (spec->kind >= STAG_NOISE_NORMAL && spec->param_mode != STAG_PARAM_SCALAR && csr->n_edges > 0 &&
-      (!spec->p0 || (spec->kind != STAG_NOISE_BERNOULLI && !spec->p1)))
-    return STAG_EINVAL;
-  const int HF = (int)HF64;
-  if (spec->deriv != 0) return STAG_EINVAL;
-
   GatArgs a{};
-  fill_gat_args(a, csr, el, er, H, neg_slope, spec, norm_scale);
-  a.ft = static_cast<const float*>(ft);     // half rows: gat_row4<DT> reads them as what they are
-  a.F = F; a.HF = HF;
-  const int prc = check_positions(spec, csr->n_edges, H, spec->kind >= STAG_NOISE_NORMAL || drop_on(drop));
-  if (prc) return prc;
-  a.out = out; a.stats = stats_out;
-  if (fill_drop(a, drop)) return STAG_EINVAL;
-  const uint64_t ftb = (uint64_t)csr->n_src * (uint64_t)HF * 2u;
-  a.ft_bytes = (ftb < (1ull << 32) && csr->n_src < (1 << 24)) ? (uint32_t)ftb : 0u;
-
+  const int rc = gat_fwd_begin(a, csr, el, er, ft, 2u, ft_dtype == STAG_DTYPE_F16 || ft_dtype == STAG_DTYPE_BF16, H, F,
+                               neg_slope, spec, norm_scale, drop, out, stats_out);
+  if (rc != kGatGo) return rc;
   // the cooperative form: F % 4 == 0, H <= 16, a row within 256 lanes, a block plan whose segments fit a batch
   const int lphp = (F % 4 == 0) ? lanes_per_head(F) : 0;
   if (lphp == 0 || H > kBlkMaxH || lphp > 64 || H * lphp > 256) return STAG_ENOSYS;
   if (!plan_in_use(plan) || !plan->block_ptr || plan->n_blocks <= 0 || plan->seg_len > kBlkEdges) return STAG_ENOSYS;
-  const size_t need = stag_gat_workspace_bytes(plan->n_seg, H, F);
-  const int plrc = check_plan(plan, kGatFwdPlan, need);
+  const int plrc = gat_fwd_plan(a, csr, plan);
   if (plrc) return plrc;
-  fill_plan(a, csr, plan);
-  if (plan->n_seg > 0) {
-    a.seg_counters = plan->seg_counters; a.n_seg = plan->n_seg;
-    a.ws_stride = (HF + 2 * H + 3) & ~3; a.ws_bytes = (uint32_t)need;
-  }
   // a lane loads 8 bytes of a row and stores 16 of out / of a segment state
   if ((reinterpret_cast<uintptr_t>(ft) & 7u) != 0 || !aligned16(out) || (a.ws && !aligned16(a.ws))) return STAG_ENOSYS;
   if (check_csr(csr)) return STAG_EINVAL;
 
-  a.block_ptr = plan->block_ptr;
-  a.lphp = lphp;
-  const int nchunk = H * lphp;
-  const int lpe = lanes_for(nchunk, 4);
-  const int cpl = nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4);
-  a.hvec = aligned16(el) && aligned16(er) && (!a.nscale || aligned16(a.nscale));
-  size_t lds_blk = (size_t)(kBlkEdges * H + 2 * kBlkUnits * H) * sizeof(float) +
-                   (size_t)(kBlkEdges + kBlkUnits + 4) * sizeof(int) + (size_t)kBlkUnits * sizeof(int4);
-  if (lds_blk < STAG_GAT_HALF_LDS_MIN) lds_blk = STAG_GAT_HALF_LDS_MIN;
+  const GatBlkShape sh = gat_blk_shape(a, plan, lphp);
+  const size_t lds_blk = gat_blk_lds(H, 1, STAG_GAT_HALF_LDS_MIN);
   const dim3 gb(plan->n_blocks);
-  const bool local = plan->xcd_order != nullptr;      // the batches are XCD-local: the rows come out of an L2
   hipStream_t s = (hipStream_t)stream;
-#define STAG_HALF_LAUNCH(DT, L, Cc, N) \
-  hipLaunchKernelGGL((gat_fwd_half_block_kernel<DT, L, Cc, N>), gb, dim3(kBlkThreads), lds_blk, s, a)
-#define STAG_HALF_LAUNCH_DT(DT)                                                                     \
-  do {                                                                                              \
-    if (cpl == 4) {                                                                                 \
-      if (local) STAG_HALF_LAUNCH(DT, 64, 4, STAG_GAT_HALF_NR_LOCAL);                               \
-      else STAG_HALF_LAUNCH(DT, 64, 4, STAG_GAT_HALF_NR);                                           \
-    } else if (cpl == 2) {                                                                          \
-      if (local) STAG_HALF_LAUNCH(DT, 64, 2, STAG_GAT_HALF_NR_LOCAL);                               \
-      else STAG_HALF_LAUNCH(DT, 64, 2, STAG_GAT_HALF_NR);                                           \
-    } else switch (lpe) {                                                                           \
-      case 64: STAG_HALF_LAUNCH(DT, 64, 1, STAG_GAT_HALF_NR_NARROW); break;                         \
-      case 32: STAG_HALF_LAUNCH(DT, 32, 1, STAG_GAT_HALF_NR_NARROW); break;                         \
-      case 16: STAG_HALF_LAUNCH(DT, 16, 1, STAG_GAT_HALF_NR_NARROW); break;                         \
-      case 8: STAG_HALF_LAUNCH(DT, 8, 1, STAG_GAT_HALF_NR_NARROW); break;                           \
-      default: STAG_HALF_LAUNCH(DT, 4, 1, STAG_GAT_HALF_NR_NARROW); break;                          \
-    }                                                                                               \
-  } while (0)
-  if (ft_dtype == STAG_DTYPE_BF16) STAG_HALF_LAUNCH_DT(STAG_DTYPE_BF16);
-  else STAG_HALF_LAUNCH_DT(STAG_DTYPE_F16);
-#undef STAG_HALF_LAUNCH_DT
-#undef STAG_HALF_LAUNCH
+  const auto launch = [&](auto DT) {
+    gat_fwd_dispatch(sh, [&](auto L, auto Cc, auto rows) {
+      constexpr int NRF = gat_rows(decltype(rows)::value, STAG_GAT_HALF_NR, STAG_GAT_HALF_NR_LOCAL, STAG_GAT_HALF_NR_NARROW);
+      hipLaunchKernelGGL((gat_fwd_block_kernel<decltype(DT)::value, decltype(L)::value, decltype(Cc)::value, NRF>), gb,
+                         dim3(kBlkThreads), lds_blk, s, a);
+    });
+  };
+  if (ft_dtype == STAG_DTYPE_BF16) launch(gat_int<STAG_DTYPE_BF16>{});
+  else launch(gat_int<STAG_DTYPE_F16>{});
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
@@ -2534,15 +2256,13 @@ extern "C" int stag_gat_fwd_mc(const stag_csr* csr, const stag_plan* plan, const
   if (!aligned16(plan->units) || !aligned16(ft) || !aligned16(out) || (n_samples > 1 && out_stride % 4 != 0))
     return STAG_ENOSYS;
   const int HF = (int)HF64;
-  const int nchunk = H * lphp;
-  const int lpe = lanes_for(nchunk, 4);
-  const int cpl = nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4);
-  const int sp = cpl == 4 ? STAG_GAT_MC_SP_WIDE : STAG_GAT_MC_SP;
-  const int wsp = n_samples < sp ? n_samples : sp;
 
   GatMcArgs g{};
   GatArgs& a = g.a;
   fill_gat_args(a, csr, el, er, H, neg_slope, spec, nullptr);   // (every pass sets its own offset in the key)
+  const GatBlkShape sh = gat_blk_shape(a, plan, lphp);
+  const int sp = sh.cpl == 4 ? STAG_GAT_MC_SP_WIDE : STAG_GAT_MC_SP;
+  const int wsp = n_samples < sp ? n_samples : sp;
   a.ft = ft; a.F = F; a.HF = HF;
   const uint64_t ftb = (uint64_t)csr->n_src * (uint64_t)HF * 4u;
   a.ft_bytes = (ftb < (1ull << 32) && csr->n_src < (1 << 24)) ? (uint32_t)ftb : 0u;
@@ -2557,14 +2277,10 @@ extern "C" int stag_gat_fwd_mc(const stag_csr* csr, const stag_plan* plan, const
   }
   if (csr->n_dst == 0) return STAG_OK;
   if (check_csr(csr)) return STAG_EINVAL;
-  a.block_ptr = plan->block_ptr;
-  a.lphp = lphp;
-  a.hvec = aligned16(el) && aligned16(er);
   g.stride = (uint64_t)offset_stride;
   g.out_stride = out_stride; g.stats_stride = stats_stride;
   g.wsp = wsp;
   const dim3 gb(plan->n_blocks);
-  const bool local = plan->xcd_order != nullptr;
   hipStream_t s = (hipStream_t)stream;
   for (int32_t s0 = 0; s0 < n_samples; s0 += sp) {
     g.ns = (n_samples - s0 < sp) ? n_samples - s0 : sp;
@@ -2572,25 +2288,13 @@ extern "C" int stag_gat_fwd_mc(const stag_csr* csr, const stag_plan* plan, const
     a.key = make_key(spec->seed, off, spec->epoch);
     a.out = out + (int64_t)s0 * out_stride;
     a.stats = stats_out ? stats_out + (int64_t)s0 * stats_stride : nullptr;
-    size_t lds = (size_t)g.ns * (kBlkEdges * H + 2 * kBlkUnits * H) * sizeof(float) +
-                 (size_t)(kBlkEdges + kBlkUnits + 4) * sizeof(int) + (size_t)kBlkUnits * sizeof(int4);
-    if (lds < STAG_GAT_LDS_MIN) lds = STAG_GAT_LDS_MIN;
-    // the (LPE, CPL, NRF) stag_gat_fwd launches for the shape: the same rounds, so the same bits per sample
-#define STAG_MC_LAUNCH(L, Cc, N, P) hipLaunchKernelGGL((gat_fwd_mc_block_kernel<L, Cc, N, P>), gb, dim3(kBlkThreads), lds, s, g)
-    if (cpl == 4) {
-      if (local) STAG_MC_LAUNCH(64, 4, STAG_GAT_NR_FWD_LOCAL, STAG_GAT_MC_SP_WIDE);
-      else STAG_MC_LAUNCH(64, 4, STAG_GAT_NR_FWD, STAG_GAT_MC_SP_WIDE);
-    } else if (cpl == 2) {
-      if (local) STAG_MC_LAUNCH(64, 2, STAG_GAT_NR_FWD_LOCAL, STAG_GAT_MC_SP);
-      else STAG_MC_LAUNCH(64, 2, STAG_GAT_NR_FWD, STAG_GAT_MC_SP);
-    } else switch (lpe) {
-      case 64: STAG_MC_LAUNCH(64, 1, STAG_GAT_NR_FWD_NARROW, STAG_GAT_MC_SP); break;
-      case 32: STAG_MC_LAUNCH(32, 1, STAG_GAT_NR_FWD_NARROW, STAG_GAT_MC_SP); break;
-      case 16: STAG_MC_LAUNCH(16, 1, STAG_GAT_NR_FWD_NARROW, STAG_GAT_MC_SP); break;
-      case 8: STAG_MC_LAUNCH(8, 1, STAG_GAT_NR_FWD_NARROW, STAG_GAT_MC_SP); break;
-      default: STAG_MC_LAUNCH(4, 1, STAG_GAT_NR_FWD_NARROW, STAG_GAT_MC_SP); break;
-    }
-#undef STAG_MC_LAUNCH
+    const size_t lds = gat_blk_lds(H, g.ns, STAG_GAT_LDS_MIN);
+    gat_fwd_dispatch(sh, [&](auto L, auto Cc, auto rows) {
+      constexpr int NRF = gat_rows(decltype(rows)::value, STAG_GAT_NR_FWD, STAG_GAT_NR_FWD_LOCAL, STAG_GAT_NR_FWD_NARROW);
+      constexpr int SP = decltype(Cc)::value == 4 ? STAG_GAT_MC_SP_WIDE : STAG_GAT_MC_SP;
+      hipLaunchKernelGGL((gat_fwd_mc_block_kernel<decltype(L)::value, decltype(Cc)::value, NRF, SP>), gb,
+                         dim3(kBlkThreads), lds, s, g);
+    });
     if (hipGetLastError() != hipSuccess) return STAG_EIO;
   }
   return STAG_OK;

@@ -199,12 +199,12 @@ def test_layer_switch_is_inert_on_the_host(monkeypatch):
 
 
 def test_half_kernels_use_no_scratch():
-    """Every instantiation of gat_fwd_half_block_kernel keeps its state in registers: 2 dtypes x (5 of one chunk per
+    """Every half-row instantiation of gat_fwd_block_kernel<DT, ...> (DT 1 fp16, 2 bf16) keeps its state in registers: 2 dtypes x (5 of one chunk per
     lane + 2 x 2 wider), 0 scratch bytes, no spilled VGPR."""
     csrc = os.path.join(ROOT, "stag_amd", "csrc")
     subprocess.run(["make", "-C", csrc, "-j", "8"], check=True, stdout=subprocess.DEVNULL)
     text = open(os.path.join(csrc, "_obj", "gat.remarks")).read()
-    found = re.findall(r"Function Name: (\S*gat_fwd_half_block_kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?VGPRs Spill: (\d+)",
+    found = re.findall(r"Function Name: (\S*gat_fwd_block_kernelILi[12]E\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?VGPRs Spill: (\d+)",
                        text, re.S)
     assert len(found) == 18, [n for n, _, _ in found]
     assert all(int(s) == 0 and int(v) == 0 for _, s, v in found), [n for n, s, v in found if int(s) or int(v)]

@@ -256,7 +256,7 @@ def _cases(shapes, seg_lens):
 # ---- forward -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,H,F,seg_len", _cases([(8, 32), (4, 16)], [16, 64]))
 def test_forward_cooperative_partitioned_max(dev, oracle, name, H, F, seg_len):
-    """gat_fwd_block_kernel<LPE, 1>, one 4-channel chunk per lane and F / 4 a power of two of at most 16 lanes per head:
+    """gat_fwd_block_kernel<fp32, LPE, 1>, one 4-channel chunk per lane and F / 4 a power of two of at most 16 lanes per head:
     the last arriver fetches the row maximum partitioned (a head's lanes take every lph-th segment, 12 states at a
     time; at (8, 32) 192 segments per round, the 4100-edge row has 257 at seg_len 16)."""
     _forward_case(dev, oracle, name, H, F, seg_len)
@@ -264,14 +264,14 @@ def test_forward_cooperative_partitioned_max(dev, oracle, name, H, F, seg_len):
 
 @pytest.mark.parametrize("name,H,F,seg_len", _cases([(3, 8), (4, 40)], [16]))
 def test_forward_cooperative_plain_max(dev, oracle, name, H, F, seg_len):
-    """gat_fwd_block_kernel<LPE, 1> without the partitioned fetch: (3, 8) leaves lanes of the team without a head,
+    """gat_fwd_block_kernel<fp32, LPE, 1> without the partitioned fetch: (3, 8) leaves lanes of the team without a head,
     (4, 40) gives a head 16 lanes for 10 chunks."""
     _forward_case(dev, oracle, name, H, F, seg_len)
 
 
 @pytest.mark.parametrize("name,H,F,seg_len", _cases([(8, 64), (4, 256)], [16]))
 def test_forward_cooperative_wide_rows(dev, oracle, name, H, F, seg_len):
-    """gat_fwd_block_kernel<64, 2> and <64, 4>: 2 and 4 chunks per lane, the merge takes one segment state at a time."""
+    """gat_fwd_block_kernel<fp32, 64, 2> and <fp32, 64, 4>: 2 and 4 chunks per lane, the merge takes one segment state at a time."""
     _forward_case(dev, oracle, name, H, F, seg_len)
 
 
@@ -299,7 +299,7 @@ def test_forward_composed(dev, oracle, name):
 @pytest.mark.parametrize("dname", ["bf16", "fp16"])
 @pytest.mark.parametrize("H,F", [(8, 32), (8, 64)])
 def test_forward_half_rows(dev, oracle, H, F, dname):
-    """stag_gat_fwd_half (gat_fwd_half_block_kernel, one and two chunks per lane) through ops._gat_fwd_half_raw: the
+    """stag_gat_fwd_half (gat_fwd_block_kernel<bf16 | fp16, ...>, one and two chunks per lane) through ops._gat_fwd_half_raw: the
     oracle on the widened rows, stats against their own reference, and out / stats equal to the fp32 entry's on
     ft.float() bit for bit, as tests/test_gpu_gat_half.py asserts at narrow logits."""
     from stag_amd import ops
