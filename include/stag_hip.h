@@ -617,6 +617,41 @@ int stag_sample_kl(const stag_csr* csr, const stag_noise_spec* spec, int32_t Dn,
                    const float* mix_logw, const float* mix_loc, const float* mix_scale, int32_t K,
                    float* kl_mean, float* dp0, float* dp1, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- contrastive NLL of amortised edge noise (stag/models.py:7-25) -------------------------------------------------
+ * StagModelContrastive's extra term for an AmortizedDistribution(in, 1) over a Normal: the real edges should carry
+ * weight pos_value (1), n_edges uniformly drawn fake edges weight neg_value (0).  The reference runs the embedding MLP
+ * over an [n_edges, 2 in] concatenation of the fake endpoints' features; here the MLP is stag_edge_mlp_fwd's on other
+ * endpoints and the log-density is closed-form, so a thread per edge id e forms, in registers,
+ *     pre_j = ps[fake_src[e], j] + pd[fake_dst[e], j];   h_j = pre_j sigmoid(pre_j)
+ *     m' = bh[0] + sum_j h_j wh[j, 0];   l' = bh[1] + sum_j h_j wh[j, 1]
+ *     t_e = nlp(pos_value; loc[e], log_scale[e]) + nlp(neg_value; m', l')
+ *     nlp(v; m, l) = 0.5 ((v - m) exp(-l))^2 + l + 0.5 log(2 pi)            (= -Normal(m, exp l).log_prob(v))
+ *     nll_mean[0] = sum_e t_e / n_edges
+ * loc, log_scale [n_edges]: the real edges' parameters by edge id (the planar arrays of stag_edge_mlp_fwd).  fake_src,
+ * fake_dst [n_edges]: trusted to be row ids of ps / pd, as stag_edge_mlp_fwd trusts src / dst.  ps, pd, ldp, hidden,
+ * wh [hidden, 2] (column 0: loc, column 1: log-scale), bh [2] (may be NULL): as stag_edge_mlp_fwd with n_par = 2.
+ * Gradients of nll_mean[0] for a unit incoming gradient (each carries 1 / n_edges; each may be NULL; all five NULL: no
+ * gradient work, the same value bit for bit):
+ *     dloc[e] = -(v - m) exp(-2 l) / n_edges,  dlog_scale[e] = (1 - ((v - m) exp(-l))^2) / n_edges   (real edges)
+ *     dpre [n_edges, hidden]: d / d pre of the fake edge, through the heads and SiLU' as stag_edge_mlp_bwd forms it
+ *         (its sums over the fake out-edges of a source / fake in-edges of a destination are the gradients of ps / pd)
+ *     dwh [hidden, 2], dbh [2].
+ * One launch of 512 blocks walks the edge ids with a grid stride (per-thread fp32 sums, wave butterfly, the block's
+ * waves in order, one partial per block in `workspace`); a second small one adds the partials in index order, in
+ * double.  No floating-point atomics: two calls on the same inputs are bit-identical.
+ * STAG_EINVAL: n_edges <= 0; hidden outside 1 ... 8; ldp < hidden or ldp >= 2^30; a NULL loc / log_scale / fake_src /
+ * fake_dst / ps / pd / wh / nll_mean.  STAG_ENOMEM: workspace NULL or shorter than
+ * stag_contrastive_nll_workspace_bytes(hidden).  Every argument is checked before any device work.                */
+size_t stag_contrastive_nll_workspace_bytes(int32_t hidden);
+int stag_contrastive_nll(const float* loc, const float* log_scale, int64_t n_edges,
+                         const int32_t* fake_src, const int32_t* fake_dst,
+                         const float* ps, const float* pd, int64_t ldp, int32_t hidden,
+                         const float* wh, const float* bh,
+                         float pos_value, float neg_value,
+                         float* nll_mean,
+                         float* dloc, float* dlog_scale, float* dpre, float* dwh, float* dbh,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Attention dropout of a GAT call (stag/zoo/gat.py:122: `attn_drop(edge_softmax(...))`, 0.6 in the reference's GAT
  * scripts): a[e,h] -> a[e,h] * keep[e,h] / keep_prob after the softmax, keep[e,h] = u < keep_prob with u the uniform
  * of the mask's OWN Philox stream (seed, offset (+ *epoch)) at (global forward position, head) — regenerated in the

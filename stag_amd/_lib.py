@@ -167,6 +167,10 @@ def bind(path):
     l.stag_sample_kl_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
     l.stag_sample_kl.argtypes = [C.POINTER(Csr), C.POINTER(NoiseSpec), C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp,
                                  _vp, C.c_size_t, _vp]
+    l.stag_contrastive_nll_workspace_bytes.restype = C.c_size_t
+    l.stag_contrastive_nll_workspace_bytes.argtypes = [C.c_int32]
+    l.stag_contrastive_nll.argtypes = [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, _vp, _vp,
+                                       C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     l.stag_coldot_workspace_bytes.restype = C.c_size_t
     l.stag_coldot_workspace_bytes.argtypes = [C.c_int32]
     l.stag_coldot.argtypes = [_vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp,

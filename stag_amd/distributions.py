@@ -187,15 +187,7 @@ class AmortizedDistribution(Distribution):
             # (w = [W_src^T | W_dst^T], the bias on the destination half), then a thread per edge for
             # SiLU and the heads (ops.node_project / ops.edge_mlp, csrc/amort.hip)
             from . import ops
-            k, hid = feat.shape[1], lin.out_features
-            w = torch.cat([lin.weight[:, :k].t(), lin.weight[:, k:].t()], 1)
-            b = None if lin.bias is None else torch.cat([torch.zeros_like(lin.bias), lin.bias])
-            heads = [self.parameters_mlp[n] for n in self.new_parameter_names]
-            wh = torch.cat([hd.weight for hd in heads], 0).t()
-            bs = [hd.bias for hd in heads]
-            bh = (None if all(t is None for t in bs) else
-                  torch.cat([t if t is not None else torch.zeros(1, device=feat.device) for t in bs]))
-            P = ops.node_project(feat, w, b)
+            P, wh, bh = self._narrow_tables(feat)
             if shard:
                 # node-range shard: the per-edge MLP reads the projected row of every edge's SOURCE, local or not — the
                 # exchange carries the projected rows ([N, 2 hidden]: 8 bytes per node at hidden = 1, not the features)
@@ -232,6 +224,22 @@ class AmortizedDistribution(Distribution):
         self.new_parameters = {k: self.parameters_mlp[k](h) for k in self.new_parameter_names}
         self._base = None
         return self
+
+    def _narrow_tables(self, feat):
+        """(P, wh, bh) of the narrow form: P [N, 2 hidden] = feat . [W_src^T | W_dst^T] + [0 | b] (ops.node_project, one
+        pass over feat), the heads side by side wh [hidden, n_par] and their biases bh [n_par] (None without any).
+        Not kept between calls: the contrastive term (ops.contrastive_nll) projects feat again."""
+        from . import ops
+        lin = self.embedding_mlp[0]
+        k = feat.shape[1]
+        w = torch.cat([lin.weight[:, :k].t(), lin.weight[:, k:].t()], 1)
+        b = None if lin.bias is None else torch.cat([torch.zeros_like(lin.bias), lin.bias])
+        heads = [self.parameters_mlp[n] for n in self.new_parameter_names]
+        wh = torch.cat([hd.weight for hd in heads], 0).t()
+        bs = [hd.bias for hd in heads]
+        bh = (None if all(t is None for t in bs) else
+              torch.cat([t if t is not None else torch.zeros(1, device=feat.device) for t in bs]))
+        return ops.node_project(feat, w, b), wh, bh
 
     def _narrow(self, graph, lin):
         """The three-kernel form applies: Sequential(Linear, SiLU), hidden <= 4, every head one column wide,

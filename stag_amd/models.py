@@ -5,6 +5,7 @@ from typing import List
 
 import torch
 
+from . import ops
 from .likelihoods import CategoricalLikelihood, Likelihood
 from .random import _MASK64
 
@@ -15,6 +16,10 @@ def nll_contrastive(q_a, graph, feat):
     n, E = graph.number_of_nodes(), graph.number_of_edges()
     fake_src = torch.randint(high=n, size=[E], device=feat.device)
     fake_dst = torch.randint(high=n, size=[E], device=feat.device)
+    if ops.contrastive_why_not(q_a, graph, feat) is None:
+        # a narrow AmortizedDistribution over a Normal on device features: one launch on the projected node tables
+        # (stag_contrastive_nll), no [E, 2 in] concatenation; the same fake edges as the lines below would see
+        return ops.contrastive_nll(q_a, graph, feat, fake_src, fake_dst)
     h_fake = q_a.embedding_mlp(torch.cat([feat[fake_src], feat[fake_dst]], dim=-1))
     fake = {k: q_a.parameters_mlp[k](h_fake) for k in q_a.new_parameter_names}
     q_neg = q_a.base_distribution_class(

@@ -11,7 +11,7 @@ import ctypes as C
 import torch
 
 from . import _lib, _torch_ext
-from .graph import DEFAULT_SEG_LEN
+from .graph import DEFAULT_SEG_LEN, Graph
 from .noise import EdgeNoise
 from .random import _MASK64
 
@@ -580,6 +580,18 @@ def head_dot(ft, attn_l, attn_r):
     return _HeadDot.apply(ft, attn_l, attn_r)
 
 
+def _pre_grad_tables(g, dpre):
+    """d P[u, j] = sum over the out-edges of u, d P[v, hidden + j] = sum over the in-edges of v of dpre[e, j] (dpre
+    [E, hidden] by edge id of `g`): the aggregation kernel over explicit rows and one broadcast row of ones, on the two
+    CSR views of g.  Returns the two [N, hidden] halves."""
+    hidden = dpre.shape[1]
+    ones = torch.ones(hidden, dtype=torch.float32, device=dpre.device)
+    spec = _explicit_spec(dpre)
+    d_src, _ = _agg_raw(g.csr_t, ones, hidden, spec, _lib.REDUCE_SUM, None, None, DEFAULT_SEG_LEN, broadcast_x=True)
+    d_dst, _ = _agg_raw(g.csr, ones, hidden, spec, _lib.REDUCE_SUM, None, None, DEFAULT_SEG_LEN, broadcast_x=True)
+    return d_src, d_dst
+
+
 class _EdgeMlp(torch.autograd.Function):
     """par_c[e] = b_c + sum_j SiLU(P[src_e, j] + P[dst_e, hidden + j]) wh[j, c]: the heads of an
     AmortizedDistribution with narrow hidden / output widths (stag/distributions.py:178-191, 225-231) on the two
@@ -624,12 +636,7 @@ class _EdgeMlp(torch.autograd.Function):
         _lib.check(rc, "stag_edge_mlp_bwd")
         dP = None
         if ctx.needs_input_grad[1]:
-            # d P[u, j] = sum over the out-edges of u, d P[v, hidden + j] = sum over the in-edges of v of dpre[e, j]:
-            # the aggregation kernel over explicit rows and one broadcast row of ones, written side by side
-            ones = torch.ones(hidden, dtype=torch.float32, device=dev)
-            spec = _explicit_spec(dpre)
-            d_src, _ = _agg_raw(g.csr_t, ones, hidden, spec, _lib.REDUCE_SUM, None, None, DEFAULT_SEG_LEN, broadcast_x=True)
-            d_dst, _ = _agg_raw(g.csr, ones, hidden, spec, _lib.REDUCE_SUM, None, None, DEFAULT_SEG_LEN, broadcast_x=True)
+            d_src, d_dst = _pre_grad_tables(g, dpre)
             if getattr(g, "is_shard", False):      # P is the exchanged buffer: destinations are this rank's rows of it
                 full = torch.zeros_like(d_src)
                 full[g.loc_off:g.loc_off + g.n_rows] = d_dst
@@ -811,6 +818,108 @@ def sampled_kl_mean(noise, mixture):
         if p0.requires_grad or p1.requires_grad:
             return _SampledKlMean.apply(p0, p1, noise, mixture)
     return _sample_kl_raw(noise, mixture, False)[0].reshape(())
+
+
+# ---- the contrastive NLL of amortised edge noise (stag/models.py:7-25; csrc/contrastive.hip) ---------------------------
+# stag_contrastive_nll | the composed route (models.nll_contrastive as the reference wrote it: an [E, 2 in] concatenation of
+# the fake endpoints' features, the MLP over its E rows, two Normal objects).  The value is the same within tolerance
+# either way: a speed and memory decision only.  True because the fused training step of the reference script's model
+# (two StagLayer(GCN) over AmortizedDistribution(in, 1), StagModelContrastive) measures faster at all three shapes
+# (profiles/r13/contrastive.txt): 3.68 against 4.81 ms Cora-sized, 3.18 against 5.09 ms Pubmed-sized, 3.66 against 15.15 ms
+# at the arxiv shape (two repeats of the composed step differ by 0.03-0.05 ms); peak allocation of a step 30 / 80 / 302
+# against 306 / 869 / 2400 MiB.  The backward's two CSR views of the fake graph cost 0.11 / 0.16 / 0.41 ms of that.
+CONTRASTIVE_FUSED = True
+
+
+def contrastive_why_not(q_a, graph, feat):
+    """The first reason models.nll_contrastive keeps the composed route, or None: the term and its gradients come from
+    one stag_contrastive_nll launch on the projected tables of q_a._narrow_tables(feat).  One clause per case that has no
+    fused form."""
+    if not CONTRASTIVE_FUSED:
+        return "switch"
+    if not getattr(feat, "is_cuda", False) or feat.dim() != 2:
+        return "features"
+    mlp = getattr(q_a, "embedding_mlp", None)
+    lin = mlp[0] if mlp is not None and len(mlp) else None
+    if not isinstance(lin, torch.nn.Linear) or not q_a._narrow(graph, lin):
+        return "not narrow"
+    if q_a.base_distribution_class is not torch.distributions.Normal or list(q_a.new_parameter_names) != ["loc", "log_scale"]:
+        return "base distribution"
+    E = graph.number_of_edges()
+    par = q_a.new_parameters
+    if not isinstance(par, dict) or list(par) != ["loc", "log_scale"] or not all(
+            torch.is_tensor(t) and tuple(t.shape) == (E, 1) and t.device == feat.device for t in par.values()):
+        return "parameters"
+    if getattr(graph, "is_shard", False):
+        return "shard"
+    if E == 0:
+        return "no edges"
+    if torch.compiler.is_compiling():
+        return "compiling"
+    return None
+
+
+def _contrastive_raw(loc, log_scale, fake_src, fake_dst, P, hidden, wh, bh, want=(False,) * 5, pos=1.0, neg=0.0):
+    """One stag_contrastive_nll on fp32 contiguous tensors: (nll_mean [1], dloc, dlog_scale, dpre, dwh, dbh), a gradient
+    None where `want` does not ask for it.  P [N, >= 2 hidden]: source half | destination half, any row stride."""
+    dev = _lib.require_device(loc, log_scale, fake_src, fake_dst, P, wh, bh)
+    E = fake_src.shape[0]
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    shapes = ((E,), (E,), (E, hidden), (hidden, 2), (2,))
+    grads = [torch.empty(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, want)]
+    nbytes = _lib.lib().stag_contrastive_nll_workspace_bytes(hidden)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_contrastive_nll(_lib.ptr(loc), _lib.ptr(log_scale), E, _lib.ptr(fake_src), _lib.ptr(fake_dst),
+                                             _lib.ptr(P), _lib.ptr(P[:, hidden:]), P.stride(0), hidden, _lib.ptr(wh),
+                                             _lib.ptr(bh), pos, neg, _lib.ptr(out), *[_lib.ptr(t) for t in grads],
+                                             _lib.ptr(ws), nbytes, _lib.stream_of(dev))
+    _lib.check(rc, "stag_contrastive_nll")
+    return (out, *grads)
+
+
+class _ContrastiveNll(torch.autograd.Function):
+    """mean_e [-N(loc_e, exp(log_scale_e)).log_prob(1) - N(m'_e, exp(l'_e)).log_prob(0)] with (m', l') the heads of the
+    narrow MLP on the fake edge (fake_src_e, fake_dst_e) of the projected tables P (stag/models.py:7-25).  The forward
+    launch returns the value and, for the inputs that need one, the gradient (loc, log_scale: [E]; P: dpre [E, hidden];
+    wh, bh); the backward scales them by the incoming gradient and — only if P needs a gradient — sums dpre over the
+    fake graph's out- and in-edges (two CSR views built for this one use, a stable sort each: a deterministic
+    scatter).  Nothing [E, 2 in]-sized exists on either pass."""
+
+    @staticmethod
+    def forward(ctx, loc, log_scale, P, wh, bh, fake_src, fake_dst):
+        E, hidden = fake_src.shape[0], wh.shape[0]
+        need = ctx.needs_input_grad[:5]
+        want = (need[0], need[1], need[2], need[3], need[4] and bh is not None)
+        out, *grads = _contrastive_raw(_f32c(loc).reshape(E), _f32c(log_scale).reshape(E), fake_src, fake_dst, _f32c(P),
+                                       hidden, _f32c(wh), _f32c(bh), want)
+        ctx.save_for_backward(*grads, fake_src, fake_dst)
+        ctx.shapes = (loc.shape, log_scale.shape, P.shape[0])
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        dloc, dls, dpre, dwh, dbh, fake_src, fake_dst = ctx.saved_tensors
+        dP = None
+        if dpre is not None:
+            fake = Graph(fake_src, fake_dst, ctx.shapes[2], _trusted=True)
+            dP = torch.cat(_pre_grad_tables(fake, dpre), 1) * g
+        return (None if dloc is None else (dloc * g).reshape(ctx.shapes[0]),
+                None if dls is None else (dls * g).reshape(ctx.shapes[1]),
+                dP, None if dwh is None else dwh * g, None if dbh is None else dbh * g, None, None)
+
+
+def contrastive_nll(q_a, graph, feat, fake_src, fake_dst):
+    """The contrastive term of models.nll_contrastive for a narrow AmortizedDistribution over a Normal whose
+    condition(graph, feat) has run, on the given fake edges (node ids, one per real edge), from one
+    stag_contrastive_nll launch.  contrastive_why_not(q_a, graph, feat) says when it applies."""
+    why = contrastive_why_not(q_a, graph, feat)
+    if why is not None and why != "switch":
+        raise ValueError(f"contrastive_nll does not apply: {why}")
+    P, wh, bh = q_a._narrow_tables(feat)
+    par = q_a.new_parameters
+    return _ContrastiveNll.apply(par["loc"], par["log_scale"], P, wh, bh, fake_src.to(torch.int32).contiguous(),
+                                 fake_dst.to(torch.int32).contiguous())
 
 
 def _bwd_w_raw(csrv, x, g, D, src_scale, broadcast_x=False, spec=None, reduce_k=False, both=False,
