@@ -258,22 +258,13 @@ __global__ __launch_bounds__(256) void agg_half_merge_kernel(const HalfArgs a) {
   store8(a.out + (int64_t)row * a.ldo, k0, a.D, vec, sum);
 }
 
-#define STAG_HALF_LPE(F, lpe, ...)                 \
-  do {                                             \
-    switch (lpe) {                                 \
-      case 64: F(64, __VA_ARGS__); break;          \
-      case 32: F(32, __VA_ARGS__); break;          \
-      case 16: F(16, __VA_ARGS__); break;          \
-      default: F(8, __VA_ARGS__); break;           \
-    }                                              \
-  } while (0)
-
 template <int KIND>
 void half_fwd_kind(const HalfArgs& a, int dtype, int lpe, dim3 grid, hipStream_t s) {
-#define STAG_HALF_FWD(L, DT) hipLaunchKernelGGL((agg_half_fwd_kernel<KIND, DT, L>), grid, dim3(256), 0, s, a)
-  if (dtype == STAG_DTYPE_BF16) STAG_HALF_LPE(STAG_HALF_FWD, lpe, STAG_DTYPE_BF16);
-  else STAG_HALF_LPE(STAG_HALF_FWD, lpe, STAG_DTYPE_F16);
-#undef STAG_HALF_FWD
+  pick<64, 32, 16, 8>(lpe, [&](auto L) {
+    pick<STAG_DTYPE_BF16, STAG_DTYPE_F16>(dtype, [&](auto DT) {
+      hipLaunchKernelGGL((agg_half_fwd_kernel<KIND, decltype(DT)::value, decltype(L)::value>), grid, dim3(256), 0, s, a);
+    });
+  });
 }
 
 }  // namespace
@@ -293,9 +284,9 @@ hipError_t half_fwd_launch(const HalfArgs& a, int kind, int dtype, int32_t n_seg
   }
   if (n_seg > 0 && a.n_long > 0) {
     const dim3 mg(a.n_long, tiles);                      // one workgroup per long row and channel tile
-#define STAG_HALF_MERGE(L, _) hipLaunchKernelGGL((agg_half_merge_kernel<L>), mg, dim3(256), 0, s, a)
-    STAG_HALF_LPE(STAG_HALF_MERGE, lpe, 0);
-#undef STAG_HALF_MERGE
+    pick<64, 32, 16, 8>(lpe, [&](auto L) {
+      hipLaunchKernelGGL((agg_half_merge_kernel<decltype(L)::value>), mg, dim3(256), 0, s, a);
+    });
   }
   return hipGetLastError();
 }

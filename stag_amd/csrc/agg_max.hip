@@ -387,43 +387,26 @@ dim3 unit_grid(const MaxArgs& a, int lpe) {
   return dim3((unsigned)((a.n_units + T - 1) / T), tiles);
 }
 
-#define STAG_MAX_LPE(F, lpe, ...)                           \
-  do {                                                      \
-    switch (lpe) {                                          \
-      case 64: F(64, __VA_ARGS__); break;                   \
-      case 32: F(32, __VA_ARGS__); break;                   \
-      case 16: F(16, __VA_ARGS__); break;                   \
-      case 8: F(8, __VA_ARGS__); break;                     \
-      case 4: F(4, __VA_ARGS__); break;                     \
-      case 2: F(2, __VA_ARGS__); break;                     \
-      default: F(1, __VA_ARGS__); break;                    \
-    }                                                       \
-  } while (0)
-
 template <int KIND>
 void fwd_kind(const MaxArgs& a, int lpe, bool vec, dim3 grid, hipStream_t s) {
-#define STAG_MAX_FWD(L, V) hipLaunchKernelGGL((agg_max_fwd_kernel<KIND, L, V>), grid, dim3(256), 0, s, a)
-  if (vec) STAG_MAX_LPE(STAG_MAX_FWD, lpe, true);
-  else STAG_MAX_LPE(STAG_MAX_FWD, lpe, false);
-#undef STAG_MAX_FWD
+  pick<64, 32, 16, 8, 4, 2, 1>(lpe, vec, [&](auto L, auto V) {
+    hipLaunchKernelGGL((agg_max_fwd_kernel<KIND, decltype(L)::value, decltype(V)::value>), grid, dim3(256), 0, s, a);
+  });
 }
 
 template <int KIND, int NO>
 void bwd_kind(const MaxArgs& a, int lpe, bool vec, dim3 grid, hipStream_t s) {
-#define STAG_MAX_BWD(L, V) hipLaunchKernelGGL((agg_max_bwd_kernel<KIND, L, V, NO>), grid, dim3(256), 0, s, a)
-  if (vec) STAG_MAX_LPE(STAG_MAX_BWD, lpe, true);
-  else STAG_MAX_LPE(STAG_MAX_BWD, lpe, false);
-#undef STAG_MAX_BWD
+  pick<64, 32, 16, 8, 4, 2, 1>(lpe, vec, [&](auto L, auto V) {
+    hipLaunchKernelGGL((agg_max_bwd_kernel<KIND, decltype(L)::value, decltype(V)::value, NO>), grid, dim3(256), 0, s, a);
+  });
 }
-
-bool vec_ok(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 
 hipError_t max_fwd_launch(const MaxArgs& a, int32_t n_seg, hipStream_t s) {
   const int lpe = lanes_for((a.D + 3) / 4, 1);
-  const bool vec = a.D % 4 == 0 && a.ldx % 4 == 0 && a.ldo % 4 == 0 && vec_ok(a.x) && vec_ok(a.out) &&
-                   (n_seg == 0 || vec_ok(a.ws));
+  const bool vec = a.D % 4 == 0 && a.ldx % 4 == 0 && a.ldo % 4 == 0 && aligned16(a.x) && aligned16(a.out) &&
+                   (n_seg == 0 || aligned16(a.ws));
   const dim3 grid = unit_grid(a, lpe);
   if (grid.x > 0) {
     switch (a.kind) {
@@ -437,10 +420,9 @@ hipError_t max_fwd_launch(const MaxArgs& a, int32_t n_seg, hipStream_t s) {
   if (n_seg > 0 && a.n_long > 0) {
     const int T = 256 / lpe;
     const dim3 mg((a.n_long + T - 1) / T, grid.y);
-#define STAG_MAX_MERGE(L, V) hipLaunchKernelGGL((agg_max_merge_kernel<L, V>), mg, dim3(256), 0, s, a)
-    if (vec) STAG_MAX_LPE(STAG_MAX_MERGE, lpe, true);
-    else STAG_MAX_LPE(STAG_MAX_MERGE, lpe, false);
-#undef STAG_MAX_MERGE
+    pick<64, 32, 16, 8, 4, 2, 1>(lpe, vec, [&](auto L, auto V) {
+      hipLaunchKernelGGL((agg_max_merge_kernel<decltype(L)::value, decltype(V)::value>), mg, dim3(256), 0, s, a);
+    });
   }
   return hipGetLastError();
 }
@@ -451,8 +433,8 @@ hipError_t max_bwd_launch(const MaxArgs& a, int32_t n_seg, hipStream_t s) {
   if (n_prep > 0)
     hipLaunchKernelGGL(agg_max_prep_kernel, dim3((unsigned)((n_prep + 255) / 256)), dim3(256), 0, s, a);
   const int lpe = lanes_for((a.D + 3) / 4, 1);
-  const bool vec = a.D % 4 == 0 && a.ldx % 4 == 0 && a.ldd % 4 == 0 && vec_ok(a.x) && (!a.dx || vec_ok(a.dx)) &&
-                   (!a.dp0 || (vec_ok(a.dp0) && vec_ok(a.dp1))) && (n_seg == 0 || vec_ok(a.ws));
+  const bool vec = a.D % 4 == 0 && a.ldx % 4 == 0 && a.ldd % 4 == 0 && aligned16(a.x) && (!a.dx || aligned16(a.dx)) &&
+                   (!a.dp0 || (aligned16(a.dp0) && aligned16(a.dp1))) && (n_seg == 0 || aligned16(a.ws));
   const dim3 grid = unit_grid(a, lpe);
   const bool grad = a.dp0 != nullptr;
   if (grid.x > 0) {
@@ -473,9 +455,9 @@ hipError_t max_bwd_launch(const MaxArgs& a, int32_t n_seg, hipStream_t s) {
   if (n_seg > 0 && a.n_long > 0) {
     const int T = 256 / lpe;
     const dim3 mg((a.n_long + T - 1) / T, grid.y);
-#define STAG_MAX_MERGE(L, _) hipLaunchKernelGGL((agg_max_bwd_merge_kernel<L>), mg, dim3(256), 0, s, a)
-    STAG_MAX_LPE(STAG_MAX_MERGE, lpe, 0);
-#undef STAG_MAX_MERGE
+    pick<64, 32, 16, 8, 4, 2, 1>(lpe, [&](auto L) {
+      hipLaunchKernelGGL((agg_max_bwd_merge_kernel<decltype(L)::value>), mg, dim3(256), 0, s, a);
+    });
   }
   return hipGetLastError();
 }

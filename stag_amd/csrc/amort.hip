@@ -24,6 +24,8 @@
 
 namespace {
 using stag::aligned16;
+using stag::lanes_per_head;
+using stag::pick;
 using stag::load4;
 using stag::team_sum;
 
@@ -467,36 +469,24 @@ inline int lpe_for(int K, int CT) {
 inline int ct_for(int C) { return C <= 2 ? 2 : C <= 4 ? 4 : C <= 8 ? 8 : 16; }
 inline int ht_for(int h) { return h <= 1 ? 1 : h <= 2 ? 2 : h <= 4 ? 4 : 8; }
 
-#define STAG_NP_DISPATCH(KERNEL, lpe, ct, grid, s, ...)                                                       \
-  do {                                                                                                        \
-    switch (lpe * 100 + ct) {                                                                                 \
-      case 802:  hipLaunchKernelGGL((KERNEL<8, 2>), grid, dim3(256), 0, s, __VA_ARGS__); break;               \
-      case 804:  hipLaunchKernelGGL((KERNEL<8, 4>), grid, dim3(256), 0, s, __VA_ARGS__); break;               \
-      case 808:  hipLaunchKernelGGL((KERNEL<8, 8>), grid, dim3(256), 0, s, __VA_ARGS__); break;               \
-      case 1602: hipLaunchKernelGGL((KERNEL<16, 2>), grid, dim3(256), 0, s, __VA_ARGS__); break;              \
-      case 1604: hipLaunchKernelGGL((KERNEL<16, 4>), grid, dim3(256), 0, s, __VA_ARGS__); break;              \
-      case 1608: hipLaunchKernelGGL((KERNEL<16, 8>), grid, dim3(256), 0, s, __VA_ARGS__); break;              \
-      case 1616: hipLaunchKernelGGL((KERNEL<16, 16>), grid, dim3(256), 0, s, __VA_ARGS__); break;             \
-      case 3202: hipLaunchKernelGGL((KERNEL<32, 2>), grid, dim3(256), 0, s, __VA_ARGS__); break;              \
-      case 3204: hipLaunchKernelGGL((KERNEL<32, 4>), grid, dim3(256), 0, s, __VA_ARGS__); break;              \
-      case 3208: hipLaunchKernelGGL((KERNEL<32, 8>), grid, dim3(256), 0, s, __VA_ARGS__); break;              \
-      case 3216: hipLaunchKernelGGL((KERNEL<32, 16>), grid, dim3(256), 0, s, __VA_ARGS__); break;             \
-      case 6402: hipLaunchKernelGGL((KERNEL<64, 2>), grid, dim3(256), 0, s, __VA_ARGS__); break;              \
-      case 6404: hipLaunchKernelGGL((KERNEL<64, 4>), grid, dim3(256), 0, s, __VA_ARGS__); break;              \
-      case 6408: hipLaunchKernelGGL((KERNEL<64, 8>), grid, dim3(256), 0, s, __VA_ARGS__); break;              \
-      default:   hipLaunchKernelGGL((KERNEL<64, 16>), grid, dim3(256), 0, s, __VA_ARGS__); break;             \
-    }                                                                                                         \
-  } while (0)
+// launch(L, CT) for node_project's lanes per row and column tile.  lpe_for gives no fewer lanes than ct, so there is
+// no <8, 16> kernel: a tile of 16 has the ladder 16 32 64, and as everywhere the last value is the default.
+template <class Launch>
+void np_dispatch(int lpe, int ct, const Launch& launch) {
+  pick<2, 4, 8, 16>(ct, [&](auto CT) {
+    if constexpr (decltype(CT)::value == 16) pick<16, 32, 64>(lpe, [&](auto L) { launch(L, CT); });
+    else pick<8, 16, 32, 64>(lpe, [&](auto L) { launch(L, CT); });
+  });
+}
 
-#define STAG_HT_DISPATCH(KERNEL, ht, grid, s, ...)                                                            \
-  do {                                                                                                        \
-    switch (ht) {                                                                                             \
-      case 1: hipLaunchKernelGGL((KERNEL<1>), grid, dim3(256), 0, s, __VA_ARGS__); break;                     \
-      case 2: hipLaunchKernelGGL((KERNEL<2>), grid, dim3(256), 0, s, __VA_ARGS__); break;                     \
-      case 4: hipLaunchKernelGGL((KERNEL<4>), grid, dim3(256), 0, s, __VA_ARGS__); break;                     \
-      default: hipLaunchKernelGGL((KERNEL<8>), grid, dim3(256), 0, s, __VA_ARGS__); break;                    \
-    }                                                                                                         \
-  } while (0)
+// first-stage blocks of a reduction to nv values over n_rows rows: fewer when a partial is large (K = 1433, C = 16:
+// 92 KB each), and no more teams than rows
+inline int red_blocks(int nv, int lpe, int64_t n_rows) {
+  int nb = kRedBlocks;
+  while (nb > 16 && (size_t)nb * nv * sizeof(float) > (32u << 20)) nb >>= 1;
+  while (nb > 1 && (int64_t)(nb / 2) * (256 / lpe) >= n_rows) nb >>= 1;
+  return nb;
+}
 
 }  // namespace
 
@@ -516,7 +506,10 @@ int stag_node_project_fwd(const float* x, int64_t ldx, int64_t n_rows, int32_t K
   const int64_t rows_per_block = (int64_t)(256 / lpe) * kFwdRows;
   const dim3 grid((unsigned)((n_rows + rows_per_block - 1) / rows_per_block));
   hipStream_t s = (hipStream_t)stream;
-  STAG_NP_DISPATCH(node_project_fwd_kernel, lpe, ct, grid, s, x, ldx, (int)n_rows, K, w, b, C, vec, y);
+  np_dispatch(lpe, ct, [&](auto L, auto CT) {
+    hipLaunchKernelGGL((node_project_fwd_kernel<decltype(L)::value, decltype(CT)::value>), grid, dim3(256), 0, s, x, ldx,
+                       (int)n_rows, K, w, b, C, vec, y);
+  });
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
@@ -535,14 +528,14 @@ int stag_node_project_bwd(const float* x, int64_t ldx, int64_t n_rows, int32_t K
   }
   if (!x || !w || !gy) return STAG_EINVAL;
   const int ct = ct_for(C), lpe = lpe_for(K, ct);
-  // fewer first-stage blocks when a partial is large (K = 1433, C = 16: 92 KB each)
-  int nb = kRedBlocks;
-  while (nb > 16 && (size_t)nb * nv * sizeof(float) > (32u << 20)) nb >>= 1;
-  while (nb > 1 && (int64_t)(nb / 2) * (256 / lpe) >= n_rows) nb >>= 1;    // no more teams than rows
+  const int nb = red_blocks(nv, lpe, n_rows);
   if (!workspace || workspace_bytes < (size_t)nb * nv * sizeof(float)) return STAG_ENOMEM;
   const bool vec = (K % 4 == 0) && (ldx % 4 == 0) && aligned16(x) && (!dx || (aligned16(dx) && lddx % 4 == 0));
   float* part = static_cast<float*>(workspace);
-  STAG_NP_DISPATCH(node_project_bwd_kernel, lpe, ct, dim3(nb), s, x, ldx, (int)n_rows, K, w, C, gy, vec, dx, lddx, part);
+  np_dispatch(lpe, ct, [&](auto L, auto CT) {
+    hipLaunchKernelGGL((node_project_bwd_kernel<decltype(L)::value, decltype(CT)::value>), dim3(nb), dim3(256), 0, s, x, ldx,
+                       (int)n_rows, K, w, C, gy, vec, dx, lddx, part);
+  });
   hipLaunchKernelGGL(reduce_final_kernel, dim3(nv), dim3(256), 0, s, part, nb, nv, dw, K * C, db,
                      (const float*)nullptr, 1.0f);
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
@@ -555,24 +548,17 @@ int stag_head_dot_fwd(const float* x, int64_t ldx, int64_t n_rows, int32_t G, in
   if (n_rows == 0) return STAG_OK;
   const int K = G * F;
   if (!x || !w || !y || ldx < K || ldx % 4 != 0 || !aligned16(x) || !aligned16(w)) return STAG_EINVAL;
-  int gl = 1;                                     // lanes per head: F / 4 rounded up to a power of two
-  while (gl * 4 < F) gl <<= 1;
+  const int gl = lanes_per_head(F);
   const int lpe = lpe_for(G * gl * 4, 1) < gl ? gl : lpe_for(G * gl * 4, 1);
   const int64_t rows_per_block = (int64_t)(256 / lpe) * kFwdRows;
   const dim3 grid((unsigned)((n_rows + rows_per_block - 1) / rows_per_block));
   hipStream_t s = (hipStream_t)stream;
-#define STAG_HD_FWD(L)                                                                                          \
-  do {                                                                                                          \
-    if (C == 1) hipLaunchKernelGGL((head_dot_fwd_kernel<L, 1>), grid, dim3(256), 0, s, x, ldx, (int)n_rows, K, F, gl, w, y); \
-    else        hipLaunchKernelGGL((head_dot_fwd_kernel<L, 2>), grid, dim3(256), 0, s, x, ldx, (int)n_rows, K, F, gl, w, y); \
-  } while (0)
-  switch (lpe) {
-    case 8: STAG_HD_FWD(8); break;
-    case 16: STAG_HD_FWD(16); break;
-    case 32: STAG_HD_FWD(32); break;
-    default: STAG_HD_FWD(64); break;
-  }
-#undef STAG_HD_FWD
+  pick<8, 16, 32, 64>(lpe, [&](auto L) {
+    pick<1, 2>(C, [&](auto Cc) {
+      hipLaunchKernelGGL((head_dot_fwd_kernel<decltype(L)::value, decltype(Cc)::value>), grid, dim3(256), 0, s, x, ldx,
+                         (int)n_rows, K, F, gl, w, y);
+    });
+  });
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
@@ -590,26 +576,17 @@ int stag_head_dot_bwd(const float* x, int64_t ldx, int64_t n_rows, int32_t G, in
   }
   if (!x || !w || !gy || ldx < K || ldx % 4 != 0 || !aligned16(x) || !aligned16(w)) return STAG_EINVAL;
   if (dx && (lddx < K || lddx % 4 != 0 || !aligned16(dx))) return STAG_EINVAL;
-  int gl = 1;
-  while (gl * 4 < F) gl <<= 1;
+  const int gl = lanes_per_head(F);
   const int lpe = lpe_for(G * gl * 4, 1) < gl ? gl : lpe_for(G * gl * 4, 1);
-  int nb = kRedBlocks;
-  while (nb > 16 && (size_t)nb * nv * sizeof(float) > (32u << 20)) nb >>= 1;
-  while (nb > 1 && (int64_t)(nb / 2) * (256 / lpe) >= n_rows) nb >>= 1;
+  const int nb = red_blocks(nv, lpe, n_rows);
   if (!workspace || workspace_bytes < (size_t)nb * nv * sizeof(float)) return STAG_ENOMEM;
   float* part = static_cast<float*>(workspace);
-#define STAG_HD_BWD(L)                                                                                          \
-  do {                                                                                                          \
-    if (C == 1) hipLaunchKernelGGL((head_dot_bwd_kernel<L, 1>), dim3(nb), dim3(256), 0, s, x, ldx, (int)n_rows, K, F, gl, w, gy, dx, lddx, part); \
-    else        hipLaunchKernelGGL((head_dot_bwd_kernel<L, 2>), dim3(nb), dim3(256), 0, s, x, ldx, (int)n_rows, K, F, gl, w, gy, dx, lddx, part); \
-  } while (0)
-  switch (lpe) {
-    case 8: STAG_HD_BWD(8); break;
-    case 16: STAG_HD_BWD(16); break;
-    case 32: STAG_HD_BWD(32); break;
-    default: STAG_HD_BWD(64); break;
-  }
-#undef STAG_HD_BWD
+  pick<8, 16, 32, 64>(lpe, [&](auto L) {
+    pick<1, 2>(C, [&](auto Cc) {
+      hipLaunchKernelGGL((head_dot_bwd_kernel<decltype(L)::value, decltype(Cc)::value>), dim3(nb), dim3(256), 0, s, x, ldx,
+                         (int)n_rows, K, F, gl, w, gy, dx, lddx, part);
+    });
+  });
   if (dw)
     hipLaunchKernelGGL(reduce_final_kernel, dim3(nv), dim3(256), 0, s, part, nb, nv, dw, nv, (float*)nullptr,
                        (const float*)nullptr, 1.0f);
@@ -625,8 +602,10 @@ int stag_edge_mlp_fwd(const int32_t* src, const int32_t* dst, int64_t n_edges, c
   if (!src || !dst || !ps || !pd || !wh || !par || ldp >= (1 << 30)) return STAG_EINVAL;
   const dim3 grid((unsigned)((n_edges + 255) / 256));
   hipStream_t s = (hipStream_t)stream;
-  STAG_HT_DISPATCH(edge_mlp_fwd_kernel, ht_for(hidden), grid, s, src, dst, n_edges, ps, pd, (int)ldp, hidden, wh, bh,
-                   n_par, par);
+  pick<1, 2, 4, 8>(ht_for(hidden), [&](auto HT) {
+    hipLaunchKernelGGL((edge_mlp_fwd_kernel<decltype(HT)::value>), grid, dim3(256), 0, s, src, dst, n_edges, ps, pd,
+                       (int)ldp, hidden, wh, bh, n_par, par);
+  });
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
@@ -645,8 +624,10 @@ int stag_edge_mlp_bwd(const int32_t* src, const int32_t* dst, int64_t n_edges, c
   const int ht = ht_for(hidden), nvp = ht * kMaxPar + kMaxPar;
   if (!workspace || workspace_bytes < stag_amort_workspace_bytes(nvp)) return STAG_ENOMEM;
   float* part = static_cast<float*>(workspace);
-  STAG_HT_DISPATCH(edge_mlp_bwd_kernel, ht, dim3(kRedBlocks), s, src, dst, n_edges, ps, pd, (int)ldp, hidden, wh,
-                   n_par, gpar, dpre, part);
+  pick<1, 2, 4, 8>(ht, [&](auto HT) {
+    hipLaunchKernelGGL((edge_mlp_bwd_kernel<decltype(HT)::value>), dim3(kRedBlocks), dim3(256), 0, s, src, dst, n_edges,
+                       ps, pd, (int)ldp, hidden, wh, n_par, gpar, dpre, part);
+  });
   hipLaunchKernelGGL(edge_mlp_final_kernel, dim3(nvp), dim3(256), 0, s, part, kRedBlocks, ht, hidden, n_par, dwh, dbh);
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }

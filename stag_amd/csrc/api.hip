@@ -1197,26 +1197,6 @@ int stag_agg_bwd_dp(const stag_csr* csr_t, const stag_plan* plan_t, const float*
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
-#define STAG_LPE_DISPATCH(KERNEL, lpe, vec, grid, s, args)                                      \
-  do {                                                                                          \
-    switch (lpe) {                                                                              \
-      case 64: if (vec) hipLaunchKernelGGL((KERNEL<64, true>), grid, dim3(256), 0, s, args);    \
-               else     hipLaunchKernelGGL((KERNEL<64, false>), grid, dim3(256), 0, s, args); break; \
-      case 32: if (vec) hipLaunchKernelGGL((KERNEL<32, true>), grid, dim3(256), 0, s, args);    \
-               else     hipLaunchKernelGGL((KERNEL<32, false>), grid, dim3(256), 0, s, args); break; \
-      case 16: if (vec) hipLaunchKernelGGL((KERNEL<16, true>), grid, dim3(256), 0, s, args);    \
-               else     hipLaunchKernelGGL((KERNEL<16, false>), grid, dim3(256), 0, s, args); break; \
-      case 8:  if (vec) hipLaunchKernelGGL((KERNEL<8, true>), grid, dim3(256), 0, s, args);     \
-               else     hipLaunchKernelGGL((KERNEL<8, false>), grid, dim3(256), 0, s, args); break;  \
-      case 4:  if (vec) hipLaunchKernelGGL((KERNEL<4, true>), grid, dim3(256), 0, s, args);     \
-               else     hipLaunchKernelGGL((KERNEL<4, false>), grid, dim3(256), 0, s, args); break;  \
-      case 2:  if (vec) hipLaunchKernelGGL((KERNEL<2, true>), grid, dim3(256), 0, s, args);     \
-               else     hipLaunchKernelGGL((KERNEL<2, false>), grid, dim3(256), 0, s, args); break;  \
-      default: if (vec) hipLaunchKernelGGL((KERNEL<1, true>), grid, dim3(256), 0, s, args);     \
-               else     hipLaunchKernelGGL((KERNEL<1, false>), grid, dim3(256), 0, s, args); break;  \
-    }                                                                                           \
-  } while (0)
-
 int stag_noise_materialize(const stag_csr* csr, const stag_plan* plan, const stag_noise_spec* spec,
                            int32_t Dn, float* w, int64_t ldw, float* norm_scale, void* stream) {
   int rc = check_csr(csr);
@@ -1250,7 +1230,9 @@ int stag_noise_materialize(const stag_csr* csr, const stag_plan* plan, const sta
   const bool vec = (Dn % 4 == 0) && (ldw % 4 == 0) && aligned16(w) && (!a.norm_scale || aligned16(norm_scale));
   const dim3 grid((a.n_units + 256 / lpe - 1) / (256 / lpe), (nchunk + lpe - 1) / lpe);
   hipStream_t s = (hipStream_t)stream;
-  STAG_LPE_DISPATCH(noise_materialize_kernel, lpe, vec, grid, s, a);
+  pick<64, 32, 16, 8, 4, 2, 1>(lpe, vec, [&](auto L, auto V) {
+    hipLaunchKernelGGL((noise_materialize_kernel<decltype(L)::value, decltype(V)::value>), grid, dim3(256), 0, s, a);
+  });
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
@@ -1310,8 +1292,10 @@ int stag_sample_kl(const stag_csr* csr, const stag_noise_spec* spec, int32_t Dn,
   b.dp0 = dp0; b.dp1 = dp1;
   const dim3 grid((unsigned)nbx, (unsigned)nby);
   hipStream_t s = (hipStream_t)stream;
-  if (K <= 2) STAG_LPE_DISPATCH(sample_kl_kernel2, lpe, edge, grid, s, b);
-  else STAG_LPE_DISPATCH(sample_kl_kernel8, lpe, edge, grid, s, b);
+  pick<64, 32, 16, 8, 4, 2, 1>(lpe, edge, [&](auto L, auto V) {
+    if (K <= 2) hipLaunchKernelGGL((sample_kl_kernel2<decltype(L)::value, decltype(V)::value>), grid, dim3(256), 0, s, b);
+    else hipLaunchKernelGGL((sample_kl_kernel8<decltype(L)::value, decltype(V)::value>), grid, dim3(256), 0, s, b);
+  });
   const bool rows = b.want_grad && a.pmode == STAG_PARAM_PER_CHANNEL;
   const int nq = (b.want_grad && a.pmode == STAG_PARAM_SCALAR) ? 3 : 1;
   hipLaunchKernelGGL(sample_kl_final_kernel, dim3(nq + (rows ? (2 * Dn + 3) / 4 : 0)), dim3(256), 0, s, b.part, nb, nq,
@@ -1345,9 +1329,13 @@ int stag_agg_bwd_w(const stag_csr* csr, const stag_plan* plan, const float* x, i
   if (a.kind >= kNormal && a.pmode == STAG_PARAM_PER_CHANNEL) vec = vec && aligned16(a.p0) && (!a.p1 || aligned16(a.p1));
   const dim3 grid((a.n_units + 256 / lpe - 1) / (256 / lpe));
   hipStream_t s = (hipStream_t)stream;
-  if (dw1) STAG_LPE_DISPATCH(agg_bwd_w_kernel2, lpe, vec, grid, s, b);
-  else if (a.kind >= kNormal) STAG_LPE_DISPATCH(agg_bwd_w_kernel1, lpe, vec, grid, s, b);
-  else STAG_LPE_DISPATCH(agg_bwd_w_kernel0, lpe, vec, grid, s, b);
+  pick<64, 32, 16, 8, 4, 2, 1>(lpe, vec, [&](auto L, auto V) {
+    constexpr int LPE = decltype(L)::value;
+    constexpr bool VEC = decltype(V)::value;
+    if (dw1) hipLaunchKernelGGL((agg_bwd_w_kernel2<LPE, VEC>), grid, dim3(256), 0, s, b);
+    else if (a.kind >= kNormal) hipLaunchKernelGGL((agg_bwd_w_kernel1<LPE, VEC>), grid, dim3(256), 0, s, b);
+    else hipLaunchKernelGGL((agg_bwd_w_kernel0<LPE, VEC>), grid, dim3(256), 0, s, b);
+  });
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
@@ -1363,23 +1351,10 @@ int stag_segment_reduce(const float* x, int64_t ldx, int32_t D, const int32_t* o
   const dim3 grid((n_seg + 256 / lpe - 1) / (256 / lpe), (nchunk + lpe - 1) / lpe);
   const int m = reduce == STAG_REDUCE_MEAN ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;
-#define STAG_SEG_LAUNCH(L)                                                                          \
-  do {                                                                                              \
-    if (vec) hipLaunchKernelGGL((segment_reduce_kernel<L, true>), grid, dim3(256), 0, s, x, ldx, D, \
-                                offsets, n_seg, m, out, ldo);                                       \
-    else     hipLaunchKernelGGL((segment_reduce_kernel<L, false>), grid, dim3(256), 0, s, x, ldx, D,\
-                                offsets, n_seg, m, out, ldo);                                       \
-  } while (0)
-  switch (lpe) {
-    case 64: STAG_SEG_LAUNCH(64); break;
-    case 32: STAG_SEG_LAUNCH(32); break;
-    case 16: STAG_SEG_LAUNCH(16); break;
-    case 8: STAG_SEG_LAUNCH(8); break;
-    case 4: STAG_SEG_LAUNCH(4); break;
-    case 2: STAG_SEG_LAUNCH(2); break;
-    default: STAG_SEG_LAUNCH(1); break;
-  }
-#undef STAG_SEG_LAUNCH
+  pick<64, 32, 16, 8, 4, 2, 1>(lpe, vec, [&](auto L, auto V) {
+    hipLaunchKernelGGL((segment_reduce_kernel<decltype(L)::value, decltype(V)::value>), grid, dim3(256), 0, s, x, ldx, D,
+                       offsets, n_seg, m, out, ldo);
+  });
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 

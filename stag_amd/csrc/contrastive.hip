@@ -13,6 +13,9 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/stag_hip.h"
+#include "entry_args.hpp"
+
+using stag::pick;
 
 namespace {
 
@@ -135,20 +138,6 @@ __global__ __launch_bounds__(256) void contrastive_final_kernel(const float* par
   else if (dbh) dbh[k - 2 * ht] = r;
 }
 
-#define STAG_CN_DISPATCH(ht, grad, s, args)                                                                          \
-  do {                                                                                                               \
-    switch ((ht) * 2 + ((grad) ? 1 : 0)) {                                                                           \
-      case 2:  hipLaunchKernelGGL((contrastive_nll_kernel<1, false>), dim3(kRedBlocks), dim3(256), 0, s, args); break; \
-      case 3:  hipLaunchKernelGGL((contrastive_nll_kernel<1, true>), dim3(kRedBlocks), dim3(256), 0, s, args); break;  \
-      case 4:  hipLaunchKernelGGL((contrastive_nll_kernel<2, false>), dim3(kRedBlocks), dim3(256), 0, s, args); break; \
-      case 5:  hipLaunchKernelGGL((contrastive_nll_kernel<2, true>), dim3(kRedBlocks), dim3(256), 0, s, args); break;  \
-      case 8:  hipLaunchKernelGGL((contrastive_nll_kernel<4, false>), dim3(kRedBlocks), dim3(256), 0, s, args); break; \
-      case 9:  hipLaunchKernelGGL((contrastive_nll_kernel<4, true>), dim3(kRedBlocks), dim3(256), 0, s, args); break;  \
-      case 16: hipLaunchKernelGGL((contrastive_nll_kernel<8, false>), dim3(kRedBlocks), dim3(256), 0, s, args); break; \
-      default: hipLaunchKernelGGL((contrastive_nll_kernel<8, true>), dim3(kRedBlocks), dim3(256), 0, s, args); break;  \
-    }                                                                                                                \
-  } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -177,7 +166,11 @@ int stag_contrastive_nll(const float* loc, const float* log_scale, int64_t n_edg
   a.dloc = dloc; a.dls = dlog_scale; a.dpre = dpre;
   a.part = static_cast<float*>(workspace);
   hipStream_t s = (hipStream_t)stream;
-  STAG_CN_DISPATCH(ht, grad, s, a);
+  // the rung is (ht, grad) as one number, 2 ht + grad; the last of them, <8, true>, is the default
+  pick<2, 3, 4, 5, 8, 9, 16, 17>(2 * ht + (grad ? 1 : 0), [&](auto R) {
+    constexpr int r = decltype(R)::value;
+    hipLaunchKernelGGL((contrastive_nll_kernel<r / 2, (r & 1) != 0>), dim3(kRedBlocks), dim3(256), 0, s, a);
+  });
   // block 0: the value; blocks 1 ...: the head gradients (only when one of them is asked for)
   hipLaunchKernelGGL(contrastive_final_kernel, dim3((dwh || dbh) ? nv : 1), dim3(256), 0, s, a.part, kRedBlocks, nv,
                      hidden, 1.0 / (double)n_edges, nll_mean, dwh, dbh);

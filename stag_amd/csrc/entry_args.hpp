@@ -1,7 +1,7 @@
 // entry_args.hpp — host side only: how an entry point of include/stag_hip.h reads its stag_csr, stag_noise_spec and
 // stag_plan.  One definition of every check and of the spec -> kernel-argument translation; api.hip, gat.hip and
 // agg_half.hip compose them in the order that gives each entry point its return codes, and take every decision
-// before any device work.
+// before any device work.  And how every source gets from a runtime lane count to a kernel's template argument: pick.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -20,6 +20,32 @@ inline int lanes_for(int nchunk, int min_lanes) {
   int lpe = min_lanes;
   while (lpe < nchunk && lpe < 64) lpe <<= 1;
   return lpe;
+}
+
+// lanes per head of a row of heads of F channels: F / 4 rounded up to a power of two (any F: callers refuse after it)
+inline int lanes_per_head(int F) {
+  int l = 1;
+  while ((int64_t)l * 4 < F) l <<= 1;
+  return l;
+}
+
+// ---- from a runtime value to a template argument ---------------------------------------------------------------------
+// The one ladder of every launch: f(std::integral_constant<int, V>{}) for the V of Vs... that equals v, the last of them
+// when none does.  A launch site lists its kernel's instantiations, the default last, and launches from a generic lambda:
+//   pick<64, 32, 16, 8, 4>(lpe, [&](auto L) { hipLaunchKernelGGL((kernel<decltype(L)::value>), grid, block, 0, s, a); });
+template <int V0, int... Vs, class F>
+inline void pick(int v, const F& f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+  else if (v == V0) f(std::integral_constant<int, V0>{});
+  else pick<Vs...>(v, f);
+}
+// ... for kernels with a bool next to it (vec): f(std::integral_constant<int, V>{}, std::bool_constant<b>{})
+template <int... Vs, class F>
+inline void pick(int v, bool b, const F& f) {
+  pick<Vs...>(v, [&](auto V) {
+    if (b) f(V, std::true_type{});
+    else f(V, std::false_type{});
+  });
 }
 
 // ---- stag_csr ------------------------------------------------------------------------------------------------------

@@ -1998,11 +1998,19 @@ __global__ __launch_bounds__(256) void gat_seg_finish_kernel(const float* ws, in
 
 }  // namespace
 
-// lanes per head of the cooperative kernels: F / 4 rounded up to a power of two (F % 4 == 0)
-static int lanes_per_head(int F) {
-  int l = 1;
-  while (l * 4 < F) l <<= 1;
-  return l;
+// The shape rule of the cooperative kernels: a head takes lphp = lanes_per_head(F) lanes (the backward's head sums are
+// DPP butterflies, and the forward keeps the backward's mapping; lanes past a head's channels idle), a row H * lphp of
+// them, at most 256.  Returns lphp, or 0 where they have no shape for (H, F): F % 4 != 0, H > 16 or a wider row.
+static int gat_blk_lphp(int H, int F) {
+  const int lphp = (F % 4 == 0) ? lanes_per_head(F) : 0;
+  return (lphp == 0 || H > kBlkMaxH || lphp > 64 || H * lphp > 256) ? 0 : lphp;
+}
+
+// what a narrow (32-bit) buffer descriptor takes as the extent of `rows` rows of row_bytes each: 0 where it cannot
+// name them all, and the kernel reads through plain addresses
+static uint32_t narrow_extent(int64_t rows, uint64_t row_bytes) {
+  const uint64_t bytes = (uint64_t)rows * row_bytes;
+  return (bytes < (1ull << 32) && rows < (1 << 24)) ? (uint32_t)bytes : 0u;
 }
 
 // attention dropout of a call: 0 = none / set, STAG_EINVAL for a bad probability
@@ -2068,8 +2076,7 @@ static int gat_fwd_begin(GatArgs& a, const stag_csr* csr, const float* el, const
   if (prc) return prc;
   a.out = out; a.stats = stats_out;
   if (fill_drop(a, drop)) return STAG_EINVAL;
-  const uint64_t ftb = (uint64_t)csr->n_src * (uint64_t)a.HF * ft_esize;
-  a.ft_bytes = (ftb < (1ull << 32) && csr->n_src < (1 << 24)) ? (uint32_t)ftb : 0u;
+  a.ft_bytes = narrow_extent(csr->n_src, (uint64_t)a.HF * ft_esize);
   return kGatGo;
 }
 
@@ -2091,44 +2098,47 @@ static int gat_fwd_plan(GatArgs& a, const stag_csr* csr, const stag_plan* plan) 
 // fields only it reads, and what picks its kernel.  A head takes lphp lanes, a row H * lphp: lpe lanes per unit with cpl
 // chunks of 4 channels each.  local: the batches are XCD-local, the rows come out of an L2.
 struct GatBlkShape { int lpe, cpl; bool local; };
-static GatBlkShape gat_blk_shape(GatArgs& a, const stag_plan* plan, int lphp) {
-  a.block_ptr = plan->block_ptr;
-  a.lphp = lphp;
-  a.hvec = aligned16(a.el) && aligned16(a.er) && (!a.nscale || aligned16(a.nscale));
-  const int nchunk = a.H * lphp;
+static GatBlkShape gat_blk_lanes(int H, int lphp, const stag_plan* plan) {
+  const int nchunk = H * lphp;
   return {lanes_for(nchunk, 4), nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4), plan->xcd_order != nullptr};
 }
-// bytes of LDS of a workgroup that carries ns samples: logits and statistics per sample + the batch records, at least `floor`
-static size_t gat_blk_lds(int H, int ns, size_t floor) {
-  const size_t lds = (size_t)ns * (kBlkEdges * H + 2 * kBlkUnits * H) * sizeof(float) +
-                     (size_t)(kBlkEdges + kBlkUnits + 4) * sizeof(int) + (size_t)kBlkUnits * sizeof(int4);
+// ... and the block fields of a filled argument block.  hvec: every [n, H] array the kernel reads takes dwordx4 loads:
+// el and nscale, and the rest the pass reads (er; the backward's stats or pack), whose alignment the caller states.
+static GatBlkShape gat_blk_shape(GatArgs& a, const stag_plan* plan, int lphp, bool rest_aligned) {
+  a.block_ptr = plan->block_ptr;
+  a.lphp = lphp;
+  a.hvec = aligned16(a.el) && (!a.nscale || aligned16(a.nscale)) && rest_aligned;
+  return gat_blk_lanes(a.H, lphp, plan);
+}
+// bytes of LDS of a cooperative workgroup: `floats` floats ahead of the batch records, at least `floor`
+static size_t gat_lds(size_t floats, size_t floor) {
+  const size_t lds = floats * sizeof(float) + (size_t)(kBlkEdges + kBlkUnits + 4) * sizeof(int) +
+                     (size_t)kBlkUnits * sizeof(int4);
   return lds < floor ? floor : lds;
 }
+// ... of a forward workgroup that carries ns samples: logits and statistics per sample
+static size_t gat_blk_lds(int H, int ns, size_t floor) {
+  return gat_lds((size_t)ns * (kBlkEdges * H + 2 * kBlkUnits * H), floor);
+}
 
-// The instantiation of a cooperative forward kernel for a shape: launch(LPE, CPL, rows) with std::integral_constants,
-// rows the class of rows in flight, which each entry maps to a knob of its own — rows of one chunk per lane (at most
-// 256 floats) are kGatRowsNarrow whatever the launch; wider ones are kGatRowsWide, or kGatRowsWideLocal on XCD-local
-// batches.  stag_gat_fwd_mc goes through the same ladder as stag_gat_fwd: the same rounds, so the same bits per sample.
+// The instantiation of a cooperative kernel for a shape, forward or backward: launch(LPE, CPL, rows) with
+// std::integral_constants, rows the class of rows in flight, which each forward entry maps to a knob of its own and
+// the backward ignores — rows of one chunk per lane (at most 256 floats) are kGatRowsNarrow whatever the launch; wider
+// ones are kGatRowsWide, or kGatRowsWideLocal on XCD-local batches.  stag_gat_fwd_mc goes through the same ladder as
+// stag_gat_fwd: the same rounds, so the same bits per sample.
 enum { kGatRowsWide, kGatRowsWideLocal, kGatRowsNarrow };
 constexpr int gat_rows(int rows, int wide, int wide_local, int narrow) {
   return rows == kGatRowsWide ? wide : (rows == kGatRowsWideLocal ? wide_local : narrow);
 }
 template <int V> using gat_int = std::integral_constant<int, V>;
 template <class Launch>
-static void gat_fwd_dispatch(const GatBlkShape& sh, const Launch& launch) {
-  const gat_int<64> w;
-  const gat_int<kGatRowsNarrow> narrow;
-  if (sh.cpl == 4 && sh.local) launch(w, gat_int<4>{}, gat_int<kGatRowsWideLocal>{});
-  else if (sh.cpl == 4) launch(w, gat_int<4>{}, gat_int<kGatRowsWide>{});
-  else if (sh.cpl == 2 && sh.local) launch(w, gat_int<2>{}, gat_int<kGatRowsWideLocal>{});
-  else if (sh.cpl == 2) launch(w, gat_int<2>{}, gat_int<kGatRowsWide>{});
-  else switch (sh.lpe) {
-    case 64: launch(w, gat_int<1>{}, narrow); break;
-    case 32: launch(gat_int<32>{}, gat_int<1>{}, narrow); break;
-    case 16: launch(gat_int<16>{}, gat_int<1>{}, narrow); break;
-    case 8: launch(gat_int<8>{}, gat_int<1>{}, narrow); break;
-    default: launch(gat_int<4>{}, gat_int<1>{}, narrow); break;
-  }
+static void gat_blk_dispatch(const GatBlkShape& sh, const Launch& launch) {
+  pick<4, 2, 1>(sh.cpl, [&](auto Cc) {
+    if constexpr (decltype(Cc)::value == 1)
+      pick<64, 32, 16, 8, 4>(sh.lpe, [&](auto L) { launch(L, Cc, gat_int<kGatRowsNarrow>{}); });
+    else if (sh.local) launch(gat_int<64>{}, Cc, gat_int<kGatRowsWideLocal>{});
+    else launch(gat_int<64>{}, Cc, gat_int<kGatRowsWide>{});
+  });
 }
 
 extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const float* el,
@@ -2151,38 +2161,25 @@ extern "C" int stag_gat_fwd(const stag_csr* csr, const stag_plan* plan, const fl
   const dim3 grid((a.n_units + tpb - 1) / tpb);
   const size_t lds_bytes = (size_t)256 * H * sizeof(float);   // [teams][LPE][H]
   hipStream_t s = (hipStream_t)stream;
-  // the cooperative kernel gives a head lphp = F / 4 rounded up to a power of two lanes (the backward's head sums are
-  // DPP butterflies, and the forward keeps the backward's mapping): a row takes H * lphp lanes, at most 256
-  const int lphp = (F % 4 == 0) ? lanes_per_head(F) : 0;
-  const bool blk_ok = use_plan && plan->block_ptr && plan->n_blocks > 0 && vec && H <= kBlkMaxH && plan->seg_len <= kBlkEdges &&
-                      lphp > 0 && lphp <= 64 && H * lphp <= 256;
+  const int lphp = gat_blk_lphp(H, F);
+  const bool blk_ok = use_plan && plan->block_ptr && plan->n_blocks > 0 && vec && plan->seg_len <= kBlkEdges && lphp > 0;
   if (HF > 256 && !blk_ok) return STAG_ENOSYS;
   if (a.drop_keep > 0.f && !blk_ok) return STAG_ENOSYS;      // attention dropout lives in the cooperative kernels
   if (check_csr(csr)) return STAG_EINVAL;
   if (blk_ok) {
-    const GatBlkShape sh = gat_blk_shape(a, plan, lphp);
+    const GatBlkShape sh = gat_blk_shape(a, plan, lphp, aligned16(er));
     const size_t lds_blk = gat_blk_lds(H, 1, STAG_GAT_LDS_MIN);
     const dim3 gb(plan->n_blocks);
-    gat_fwd_dispatch(sh, [&](auto L, auto Cc, auto rows) {
+    gat_blk_dispatch(sh, [&](auto L, auto Cc, auto rows) {
       constexpr int NRF = gat_rows(decltype(rows)::value, STAG_GAT_NR_FWD, STAG_GAT_NR_FWD_LOCAL, STAG_GAT_NR_FWD_NARROW);
       hipLaunchKernelGGL((gat_fwd_block_kernel<kGatRowF32, decltype(L)::value, decltype(Cc)::value, NRF>), gb,
                          dim3(kBlkThreads), lds_blk, s, a);
     });
     return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
   }
-#define STAG_GAT_LAUNCH(L)                                                                         \
-  do {                                                                                             \
-    if (vec) hipLaunchKernelGGL((gat_fwd_kernel<L, true>), grid, dim3(256), lds_bytes, s, a);     \
-    else     hipLaunchKernelGGL((gat_fwd_kernel<L, false>), grid, dim3(256), lds_bytes, s, a);    \
-  } while (0)
-  switch (lpe) {
-    case 64: STAG_GAT_LAUNCH(64); break;
-    case 32: STAG_GAT_LAUNCH(32); break;
-    case 16: STAG_GAT_LAUNCH(16); break;
-    case 8: STAG_GAT_LAUNCH(8); break;
-    default: STAG_GAT_LAUNCH(4); break;
-  }
-#undef STAG_GAT_LAUNCH
+  pick<64, 32, 16, 8, 4>(lpe, vec, [&](auto L, auto V) {
+    hipLaunchKernelGGL((gat_fwd_kernel<decltype(L)::value, decltype(V)::value>), grid, dim3(256), lds_bytes, s, a);
+  });
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
@@ -2198,8 +2195,8 @@ extern "C" int stag_gat_fwd_half(const stag_csr* csr, const stag_plan* plan, con
                                neg_slope, spec, norm_scale, drop, out, stats_out);
   if (rc != kGatGo) return rc;
   // the cooperative form: F % 4 == 0, H <= 16, a row within 256 lanes, a block plan whose segments fit a batch
-  const int lphp = (F % 4 == 0) ? lanes_per_head(F) : 0;
-  if (lphp == 0 || H > kBlkMaxH || lphp > 64 || H * lphp > 256) return STAG_ENOSYS;
+  const int lphp = gat_blk_lphp(H, F);
+  if (lphp == 0) return STAG_ENOSYS;
   if (!plan_in_use(plan) || !plan->block_ptr || plan->n_blocks <= 0 || plan->seg_len > kBlkEdges) return STAG_ENOSYS;
   const int plrc = gat_fwd_plan(a, csr, plan);
   if (plrc) return plrc;
@@ -2207,19 +2204,17 @@ extern "C" int stag_gat_fwd_half(const stag_csr* csr, const stag_plan* plan, con
   if ((reinterpret_cast<uintptr_t>(ft) & 7u) != 0 || !aligned16(out) || (a.ws && !aligned16(a.ws))) return STAG_ENOSYS;
   if (check_csr(csr)) return STAG_EINVAL;
 
-  const GatBlkShape sh = gat_blk_shape(a, plan, lphp);
+  const GatBlkShape sh = gat_blk_shape(a, plan, lphp, aligned16(er));
   const size_t lds_blk = gat_blk_lds(H, 1, STAG_GAT_HALF_LDS_MIN);
   const dim3 gb(plan->n_blocks);
   hipStream_t s = (hipStream_t)stream;
-  const auto launch = [&](auto DT) {
-    gat_fwd_dispatch(sh, [&](auto L, auto Cc, auto rows) {
+  pick<STAG_DTYPE_BF16, STAG_DTYPE_F16>(ft_dtype, [&](auto DT) {
+    gat_blk_dispatch(sh, [&](auto L, auto Cc, auto rows) {
       constexpr int NRF = gat_rows(decltype(rows)::value, STAG_GAT_HALF_NR, STAG_GAT_HALF_NR_LOCAL, STAG_GAT_HALF_NR_NARROW);
       hipLaunchKernelGGL((gat_fwd_block_kernel<decltype(DT)::value, decltype(L)::value, decltype(Cc)::value, NRF>), gb,
                          dim3(kBlkThreads), lds_blk, s, a);
     });
-  };
-  if (ft_dtype == STAG_DTYPE_BF16) launch(gat_int<STAG_DTYPE_BF16>{});
-  else launch(gat_int<STAG_DTYPE_F16>{});
+  });
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
@@ -2250,9 +2245,9 @@ extern "C" int stag_gat_fwd_mc(const stag_csr* csr, const stag_plan* plan, const
   if (prc) return prc;
   if (spec->chunk_base != 0) return STAG_ENOSYS;   // heads are not channel-sharded
   // the cooperative form only: a block plan, F % 4 == 0, H <= 16, H * F <= 1024, a row within 256 lanes, 16-B rows
-  const int lphp = (F % 4 == 0) ? lanes_per_head(F) : 0;
+  const int lphp = gat_blk_lphp(H, F);
   if (!plan || plan->n_units <= 0 || !plan->units || !plan->block_ptr || plan->n_blocks <= 0) return STAG_ENOSYS;
-  if (lphp == 0 || H > kBlkMaxH || HF64 > 1024 || lphp > 64 || H * lphp > 256 || plan->seg_len > kBlkEdges) return STAG_ENOSYS;
+  if (lphp == 0 || HF64 > 1024 || plan->seg_len > kBlkEdges) return STAG_ENOSYS;
   if (!aligned16(plan->units) || !aligned16(ft) || !aligned16(out) || (n_samples > 1 && out_stride % 4 != 0))
     return STAG_ENOSYS;
   const int HF = (int)HF64;
@@ -2260,12 +2255,11 @@ extern "C" int stag_gat_fwd_mc(const stag_csr* csr, const stag_plan* plan, const
   GatMcArgs g{};
   GatArgs& a = g.a;
   fill_gat_args(a, csr, el, er, H, neg_slope, spec, nullptr);   // (every pass sets its own offset in the key)
-  const GatBlkShape sh = gat_blk_shape(a, plan, lphp);
+  const GatBlkShape sh = gat_blk_shape(a, plan, lphp, aligned16(er));
   const int sp = sh.cpl == 4 ? STAG_GAT_MC_SP_WIDE : STAG_GAT_MC_SP;
   const int wsp = n_samples < sp ? n_samples : sp;
   a.ft = ft; a.F = F; a.HF = HF;
-  const uint64_t ftb = (uint64_t)csr->n_src * (uint64_t)HF * 4u;
-  a.ft_bytes = (ftb < (1ull << 32) && csr->n_src < (1 << 24)) ? (uint32_t)ftb : 0u;
+  a.ft_bytes = narrow_extent(csr->n_src, (uint64_t)HF * 4u);
   fill_plan(a, csr, plan);
   a.ws_stride = (HF + 2 * H + 3) & ~3;
   const size_t need = stag_gat_workspace_bytes(plan->n_seg, H, F) * (size_t)wsp;
@@ -2289,7 +2283,7 @@ extern "C" int stag_gat_fwd_mc(const stag_csr* csr, const stag_plan* plan, const
     a.out = out + (int64_t)s0 * out_stride;
     a.stats = stats_out ? stats_out + (int64_t)s0 * stats_stride : nullptr;
     const size_t lds = gat_blk_lds(H, g.ns, STAG_GAT_LDS_MIN);
-    gat_fwd_dispatch(sh, [&](auto L, auto Cc, auto rows) {
+    gat_blk_dispatch(sh, [&](auto L, auto Cc, auto rows) {
       constexpr int NRF = gat_rows(decltype(rows)::value, STAG_GAT_NR_FWD, STAG_GAT_NR_FWD_LOCAL, STAG_GAT_NR_FWD_NARROW);
       constexpr int SP = decltype(Cc)::value == 4 ? STAG_GAT_MC_SP_WIDE : STAG_GAT_MC_SP;
       hipLaunchKernelGGL((gat_fwd_mc_block_kernel<decltype(L)::value, decltype(Cc)::value, NRF, SP>), gb,
@@ -2363,13 +2357,9 @@ extern "C" int stag_gat_bwd_edge(const stag_csr* csr, const stag_plan* plan, con
   const dim3 grid((a.n_units + tpb - 1) / tpb);
   const size_t lds_bytes = (size_t)3 * 256 * H * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-  switch (lpe) {
-    case 64: hipLaunchKernelGGL(gat_bwd_edge_kernel<64>, grid, dim3(256), lds_bytes, s, ba); break;
-    case 32: hipLaunchKernelGGL(gat_bwd_edge_kernel<32>, grid, dim3(256), lds_bytes, s, ba); break;
-    case 16: hipLaunchKernelGGL(gat_bwd_edge_kernel<16>, grid, dim3(256), lds_bytes, s, ba); break;
-    case 8: hipLaunchKernelGGL(gat_bwd_edge_kernel<8>, grid, dim3(256), lds_bytes, s, ba); break;
-    default: hipLaunchKernelGGL(gat_bwd_edge_kernel<4>, grid, dim3(256), lds_bytes, s, ba); break;
-  }
+  pick<64, 32, 16, 8, 4>(lpe, [&](auto L) {
+    hipLaunchKernelGGL(gat_bwd_edge_kernel<decltype(L)::value>, grid, dim3(256), lds_bytes, s, ba);
+  });
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
@@ -2380,6 +2370,15 @@ extern "C" size_t stag_gat_bwd_workspace_bytes(int32_t n_seg, int32_t n_seg_t, i
   const size_t a = n_seg > 0 ? (size_t)n_seg * (size_t)H : 0;
   const size_t b = n_seg_t > 0 ? (size_t)n_seg_t * (size_t)(H * F + H) : 0;
   return (a > b ? a : b) * sizeof(float);
+}
+
+// the end of a source pass: d_ft and d_el of the long source rows, from their segments' partials ws [n_seg_t][HF + H]
+static void gat_src_finish(const stag_plan* plan_t, const float* ws, int H, int HF, float* d_ft, float* d_el, hipStream_t s) {
+  if (plan_t->n_long <= 0) return;
+  hipLaunchKernelGGL(gat_seg_finish_kernel, dim3(plan_t->n_long, (HF + 15) / 16), dim3(256), 0, s, ws, HF + H, 0, HF,
+                     plan_t->long_rows, plan_t->long_seg_ptr, d_ft, HF);
+  hipLaunchKernelGGL(gat_seg_finish_kernel, dim3(plan_t->n_long, (H + 15) / 16), dim3(256), 0, s, ws, HF + H, HF, H,
+                     plan_t->long_rows, plan_t->long_seg_ptr, d_el, H);
 }
 
 extern "C" int stag_gat_bwd_two_pass(const stag_csr* csr, const stag_plan* plan, const stag_csr* csr_t,
@@ -2394,8 +2393,8 @@ extern "C" int stag_gat_bwd_two_pass(const stag_csr* csr, const stag_plan* plan,
   if (!spec || spec->kind < STAG_NOISE_NONE || spec->kind > STAG_NOISE_BERNOULLI || spec->deriv) return STAG_EINVAL;
   if (!d_el || !d_er || !d_ft || !ade_ws || H <= 0 || F <= 0) return STAG_EINVAL;
   const int64_t HF64 = (int64_t)H * F;
-  const int lph = F / 4;
-  if (H > kBlkMaxH || HF64 > 1024 || F % 4 != 0 || lph > 64 || (lph & (lph - 1)) != 0) return STAG_ENOSYS;
+  const int lphp = gat_blk_lphp(H, F);
+  if (lphp == 0 || HF64 > 1024 || lphp != F / 4) return STAG_ENOSYS;   // this form: F / 4 a power of two, no idle lanes
   if (spec->chunk_base != 0) return STAG_ENOSYS;
   if (!plan || !plan_t || !plan->block_ptr || !plan_t->block_ptr || plan->n_blocks <= 0 || plan_t->n_blocks <= 0 ||
       plan->seg_len > kBlkEdges || plan_t->seg_len > kBlkEdges)
@@ -2419,30 +2418,16 @@ extern "C" int stag_gat_bwd_two_pass(const stag_csr* csr, const stag_plan* plan,
   // the source pass's plan too, before the edge pass is enqueued
   if (check_plan_units(plan_t, 0) || check_plan_segments(plan_t, kPlanSegPtr)) return STAG_EINVAL;
   if (check_csr(csr) || check_csr(csr_t)) return STAG_EINVAL;
-  a.ft = ft; a.F = F; a.HF = HF; a.lphp = lph;
-  const uint64_t ftb = (uint64_t)csr->n_src * (uint64_t)HF * 4u;
-  a.ft_bytes = (ftb < (1ull << 32) && csr->n_src < (1 << 24)) ? (uint32_t)ftb : 0u;
-  a.block_ptr = plan->block_ptr;
-  a.hvec = aligned16(el) && aligned16(er) && aligned16(stats) && (!a.nscale || aligned16(a.nscale));
+  a.ft = ft; a.F = F; a.HF = HF;
+  a.ft_bytes = narrow_extent(csr->n_src, (uint64_t)HF * 4u);
+  const GatBlkShape sh = gat_blk_shape(a, plan, lphp, aligned16(er) && aligned16(stats));
   ba.g = g; ba.out = out; ba.ade = ade_ws; ba.d_er = d_er; ba.dw = dw; ba.ws = plan->workspace;
-  const int nchunk = (HF + 3) / 4;
-  const int lpe = lanes_for(nchunk, 4);
-  const int cpl = nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4);
-  size_t lds_e = (size_t)kBlkEdges * H * (dw ? 3 : 2) * sizeof(float) +
-                 (size_t)(kBlkEdges + kBlkUnits + 4) * sizeof(int) + (size_t)kBlkUnits * sizeof(int4);
-  if (lds_e < STAG_GAT_LDS_MIN_BWD) lds_e = STAG_GAT_LDS_MIN_BWD;
+  const size_t lds_e = gat_lds((size_t)kBlkEdges * H * (dw ? 3 : 2), STAG_GAT_LDS_MIN_BWD);
   const dim3 ge(plan->n_blocks);
-#define STAG_BLK_LAUNCH(L, Cc) hipLaunchKernelGGL((gat_bwd_edge_block_kernel<L, Cc>), ge, dim3(kBlkThreads), lds_e, s, ba)
-    if (cpl == 4) STAG_BLK_LAUNCH(64, 4);
-    else if (cpl == 2) STAG_BLK_LAUNCH(64, 2);
-    else switch (lpe) {
-      case 64: STAG_BLK_LAUNCH(64, 1); break;
-      case 32: STAG_BLK_LAUNCH(32, 1); break;
-      case 16: STAG_BLK_LAUNCH(16, 1); break;
-      case 8: STAG_BLK_LAUNCH(8, 1); break;
-      default: STAG_BLK_LAUNCH(4, 1); break;
-    }
-#undef STAG_BLK_LAUNCH
+  gat_blk_dispatch(sh, [&](auto L, auto Cc, auto) {
+    hipLaunchKernelGGL((gat_bwd_edge_block_kernel<decltype(L)::value, decltype(Cc)::value>), ge, dim3(kBlkThreads), lds_e,
+                       s, ba);
+  });
   if (plan->n_long > 0)
     hipLaunchKernelGGL(gat_seg_finish_kernel, dim3(plan->n_long, (H + 15) / 16), dim3(256), 0, s,
                        plan->workspace, H, 0, H, plan->long_rows, plan->long_seg_ptr, d_er, H);
@@ -2451,30 +2436,15 @@ extern "C" int stag_gat_bwd_two_pass(const stag_csr* csr, const stag_plan* plan,
   sa.indices = csr_t->indices; sa.nidx = csr_t->nidx;
   sa.units = plan_t->units; sa.block_ptr = plan_t->block_ptr; sa.long_rows = plan_t->long_rows;
   sa.ade = ade_ws; sa.g = g; sa.H = H; sa.F = F; sa.HF = HF;
-  const uint64_t gb = (uint64_t)csr->n_dst * (uint64_t)HF * 4u;
-  sa.g_bytes = (gb < (1ull << 32) && csr->n_dst < (1 << 24)) ? (uint32_t)gb : 0u;
+  sa.g_bytes = narrow_extent(csr->n_dst, (uint64_t)HF * 4u);
   sa.d_ft = d_ft; sa.d_el = d_el; sa.ws = plan->workspace;   // the edge pass's partials are consumed by now (stream order)
-  size_t lds_s = (size_t)kBlkEdges * H * 2 * sizeof(float) + (size_t)(kBlkEdges + kBlkUnits + 4) * sizeof(int) +
-                 (size_t)kBlkUnits * sizeof(int4);
-  if (lds_s < STAG_GAT_LDS_MIN_BWD) lds_s = STAG_GAT_LDS_MIN_BWD;
+  const size_t lds_s = gat_lds((size_t)kBlkEdges * H * 2, STAG_GAT_LDS_MIN_BWD);
   const dim3 gs(plan_t->n_blocks);
-#define STAG_BLK_LAUNCH(L, Cc) hipLaunchKernelGGL((gat_bwd_src_block_kernel<L, Cc>), gs, dim3(kBlkThreads), lds_s, s, sa)
-    if (cpl == 4) STAG_BLK_LAUNCH(64, 4);
-    else if (cpl == 2) STAG_BLK_LAUNCH(64, 2);
-    else switch (lpe) {
-      case 64: STAG_BLK_LAUNCH(64, 1); break;
-      case 32: STAG_BLK_LAUNCH(32, 1); break;
-      case 16: STAG_BLK_LAUNCH(16, 1); break;
-      case 8: STAG_BLK_LAUNCH(8, 1); break;
-      default: STAG_BLK_LAUNCH(4, 1); break;
-    }
-#undef STAG_BLK_LAUNCH
-  if (plan_t->n_long > 0) {
-    hipLaunchKernelGGL(gat_seg_finish_kernel, dim3(plan_t->n_long, (HF + 15) / 16), dim3(256), 0, s,
-                       plan->workspace, HF + H, 0, HF, plan_t->long_rows, plan_t->long_seg_ptr, d_ft, HF);
-    hipLaunchKernelGGL(gat_seg_finish_kernel, dim3(plan_t->n_long, (H + 15) / 16), dim3(256), 0, s,
-                       plan->workspace, HF + H, HF, H, plan_t->long_rows, plan_t->long_seg_ptr, d_el, H);
-  }
+  gat_blk_dispatch(sh, [&](auto L, auto Cc, auto) {
+    hipLaunchKernelGGL((gat_bwd_src_block_kernel<decltype(L)::value, decltype(Cc)::value>), gs, dim3(kBlkThreads), lds_s,
+                       s, sa);
+  });
+  gat_src_finish(plan_t, sa.ws, H, HF, d_ft, d_el, s);
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
 }
 
@@ -2553,10 +2523,8 @@ static int gat_bwd_impl(const stag_csr* csr, const stag_plan* plan, const stag_c
   if (!spec || spec->kind < STAG_NOISE_NONE || spec->kind > STAG_NOISE_BERNOULLI || spec->deriv) return STAG_EINVAL;
   if (!d_el || !d_er || !d_ft || !scratch || H <= 0 || F <= 0) return STAG_EINVAL;
   const int64_t HF64 = (int64_t)H * F;
-  if (H > kBlkMaxH || HF64 > 1024 || F % 4 != 0) return STAG_ENOSYS;
-  const int lphp = lanes_per_head(F);                   // any F % 4 == 0: lanes past a head's channels idle
-  const int lph = lphp;
-  if (lphp > 64 || H * lphp > 256) return STAG_ENOSYS;
+  const int lphp = gat_blk_lphp(H, F);                  // any F % 4 == 0: lanes past a head's channels idle
+  if (lphp == 0 || HF64 > 1024) return STAG_ENOSYS;
   if (spec->chunk_base != 0) return STAG_ENOSYS;
   if (!plan_t || !plan_t->block_ptr || plan_t->n_blocks <= 0 || plan_t->seg_len > kBlkEdges) return STAG_ENOSYS;
   if (spec->in_norm && !norm_scale) return STAG_EINVAL;
@@ -2578,13 +2546,10 @@ static int gat_bwd_impl(const stag_csr* csr, const stag_plan* plan, const stag_c
   float* dsl = scratch;
   float* pack = scratch + (size_t)csr->n_edges * H;        // 16-byte aligned whenever H % 4 == 0 (the vector form)
 
-  const int nchunk = H * lphp;                          // lanes a row takes
-  const int lpe = lanes_for(nchunk, 4);
-  const int cpl = nchunk <= 64 ? 1 : (nchunk <= 128 ? 2 : 4);
-
   // the source pass's arguments: its refusals come before the first launch too
   GatBwd1Args ba{};
   GatArgs& a = ba.f;
+  const GatBlkShape sh = gat_blk_lanes(H, lphp, plan_t);
   if (stages & STAG_GAT_BWD_SOURCE) {
     const int rc = fill_edge_args(a, csr_t, plan_t, el, er, H, neg_slope, spec, norm_scale, stats);
     if (rc) return rc;
@@ -2594,50 +2559,30 @@ static int gat_bwd_impl(const stag_csr* csr, const stag_plan* plan, const stag_c
 
   // 1. sdot[v,h] = <G[v,h,:], out[v,h,:]>
   if (stages & STAG_GAT_BWD_ROWDOT) {
-    const int rl = lpe < lph ? lph : lpe;                       // a head's lanes inside one team
+    const int rl = sh.lpe < lphp ? lphp : sh.lpe;               // a head's lanes inside one team
     const int64_t rpb = (int64_t)(256 / rl) * kRowdotRows;
     const dim3 gr((unsigned)((csr->n_dst + rpb - 1) / rpb));
-    switch (rl) {
-      case 64: hipLaunchKernelGGL((gat_rowdot_kernel<64>), gr, dim3(256), 0, s, g, out, csr->n_dst, H, F, HF, lphp, er, stats, pack); break;
-      case 32: hipLaunchKernelGGL((gat_rowdot_kernel<32>), gr, dim3(256), 0, s, g, out, csr->n_dst, H, F, HF, lphp, er, stats, pack); break;
-      case 16: hipLaunchKernelGGL((gat_rowdot_kernel<16>), gr, dim3(256), 0, s, g, out, csr->n_dst, H, F, HF, lphp, er, stats, pack); break;
-      case 8: hipLaunchKernelGGL((gat_rowdot_kernel<8>), gr, dim3(256), 0, s, g, out, csr->n_dst, H, F, HF, lphp, er, stats, pack); break;
-      default: hipLaunchKernelGGL((gat_rowdot_kernel<4>), gr, dim3(256), 0, s, g, out, csr->n_dst, H, F, HF, lphp, er, stats, pack); break;
-    }
+    pick<64, 32, 16, 8, 4>(rl, [&](auto L) {
+      hipLaunchKernelGGL((gat_rowdot_kernel<decltype(L)::value>), gr, dim3(256), 0, s, g, out, csr->n_dst, H, F, HF, lphp,
+                         er, stats, pack);
+    });
   }
 
   // 2. the source-major pass
   if (stages & STAG_GAT_BWD_SOURCE) {
-  a.ft = ft; a.F = F; a.HF = HF; a.lphp = lphp;
-  a.block_ptr = plan_t->block_ptr;
-  a.hvec = aligned16(el) && aligned16(pack) && (!a.nscale || aligned16(a.nscale));
+  a.ft = ft; a.F = F; a.HF = HF;
+  gat_blk_shape(a, plan_t, lphp, aligned16(pack));     // (er and the statistics travel in pack)
   ba.g = g; ba.pack = pack; ba.d_ft = d_ft; ba.d_el = d_el; ba.dsl = dsl; ba.dw = dw;
   ba.dp_part = dp_ws;
   ba.ws = plan ? plan->workspace : nullptr;
   ba.eid_is_pos = csr->eid ? 0 : 1;
-  const uint64_t gb = (uint64_t)csr->n_dst * (uint64_t)HF * 4u;
-  ba.g_bytes = (gb < (1ull << 32) && csr->n_dst < (1 << 24)) ? (uint32_t)gb : 0u;
-  size_t lds_s = (size_t)kBlkEdges * H * ((dw || dp_ws) ? 4 : 3) * sizeof(float) + (size_t)(kBlkEdges + kBlkUnits + 4) * sizeof(int) +
-                 (size_t)kBlkUnits * sizeof(int4);
-  if (lds_s < STAG_GAT_LDS_MIN_ONE) lds_s = STAG_GAT_LDS_MIN_ONE;
+  ba.g_bytes = narrow_extent(csr->n_dst, (uint64_t)HF * 4u);
+  const size_t lds_s = gat_lds((size_t)kBlkEdges * H * ((dw || dp_ws) ? 4 : 3), STAG_GAT_LDS_MIN_ONE);
   const dim3 gs(plan_t->n_blocks);
-#define STAG_BLK_LAUNCH(L, Cc) hipLaunchKernelGGL((gat_bwd_one_kernel<L, Cc>), gs, dim3(kBlkThreads), lds_s, s, ba)
-    if (cpl == 4) STAG_BLK_LAUNCH(64, 4);
-    else if (cpl == 2) STAG_BLK_LAUNCH(64, 2);
-    else switch (lpe) {
-      case 64: STAG_BLK_LAUNCH(64, 1); break;
-      case 32: STAG_BLK_LAUNCH(32, 1); break;
-      case 16: STAG_BLK_LAUNCH(16, 1); break;
-      case 8: STAG_BLK_LAUNCH(8, 1); break;
-      default: STAG_BLK_LAUNCH(4, 1); break;
-    }
-#undef STAG_BLK_LAUNCH
-  if (plan_t->n_long > 0) {
-    hipLaunchKernelGGL(gat_seg_finish_kernel, dim3(plan_t->n_long, (HF + 15) / 16), dim3(256), 0, s,
-                       plan->workspace, HF + H, 0, HF, plan_t->long_rows, plan_t->long_seg_ptr, d_ft, HF);
-    hipLaunchKernelGGL(gat_seg_finish_kernel, dim3(plan_t->n_long, (H + 15) / 16), dim3(256), 0, s,
-                       plan->workspace, HF + H, HF, H, plan_t->long_rows, plan_t->long_seg_ptr, d_el, H);
-  }
+  gat_blk_dispatch(sh, [&](auto L, auto Cc, auto) {
+    hipLaunchKernelGGL((gat_bwd_one_kernel<decltype(L)::value, decltype(Cc)::value>), gs, dim3(kBlkThreads), lds_s, s, ba);
+  });
+  gat_src_finish(plan_t, ba.ws, H, HF, d_ft, d_el, s);
   }
 
   // 3. d er: the in-edges of a row are contiguous in dsl (the source pass's partials are consumed by now)

@@ -12,9 +12,9 @@ ASM = """\t.text
 {k1}:
 .Lfunc_begin{n}:
 \ts_cbranch_scc1 .LBB{n}_2
-.Ltmp{t}:
+.Ltmp{t}:                                 ;     Child Loop BB{n}_2 Depth 2
 \tv_add_f32 v0, v1, v2
-.LBB{n}_2:
+.LBB{n}_2:                                ;   in Loop: Header=BB{n}_1 Depth=1
 \ts_endpgm
 .Lfunc_end{n}:
 \t.amdhsa_kernel {k1}

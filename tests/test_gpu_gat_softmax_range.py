@@ -418,7 +418,8 @@ def _backward_case(dev, oracle, monkeypatch, name, H, F, forms, slope=None):
     monkeypatch.setattr(ops, "_GAT_BWD_FUSED", True)
 
 
-@pytest.mark.parametrize("name,H,F,seg_len", _cases([(8, 32), (3, 8), (8, 64)], [16]))
+@pytest.mark.parametrize("name,H,F,seg_len", _cases([(8, 32), (3, 8), (8, 64),
+                                                     (1, 16), (4, 16), (8, 16)], [16]))      # 4, 16 and 32 lanes per row
 def test_backward_forms(dev, oracle, monkeypatch, name, H, F, seg_len):
     """d el, d er, d ft (and d w of the explicit weights) through the one-gather backward (stag_gat_bwd), the two-pass
     form (stag_gat_bwd_two_pass) and with the fused backward off — stag_gat_bwd_edge plus aggregations at (8, 32) and

@@ -71,7 +71,7 @@ GRAPHS = {
 }
 
 
-@pytest.mark.parametrize("D", [1, 3, 4, 12, 50, 128, 256, 300, 1433])
+@pytest.mark.parametrize("D", [1, 3, 4, 8, 12, 32, 50, 128, 256, 300, 1433])     # 8, 32: 2 and 8 lanes per row
 @pytest.mark.parametrize("gname", list(GRAPHS))
 def test_forward_exact_across_widths(dev, D, gname):
     g = GRAPHS[gname](dev)
@@ -268,7 +268,7 @@ def test_backward_vi_parameters(dev, kind, mode, relu, D):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
-@pytest.mark.parametrize("D", [3, 64, 256])
+@pytest.mark.parametrize("D", [3, 8, 32, 64, 256])               # 8, 32: 2 and 8 lanes per row
 def test_backward_explicit_weights(dev, D):
     from stag_amd import ops
     g = random_graph(400, 5000, seed=12, hub=600, device=dev)

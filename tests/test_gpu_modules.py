@@ -719,7 +719,7 @@ def _gat_torch_reference(src, dst, n, el, er, ft, w, neg_slope):
     return torch.zeros_like(ft).index_add_(0, dst, a.unsqueeze(-1) * ft[src])
 
 
-@pytest.mark.parametrize("H,F", [(8, 32), (3, 4), (2, 16)])
+@pytest.mark.parametrize("H,F", [(8, 32), (3, 4), (2, 16), (8, 16)])      # (8, 16): 32 lanes per row, forward and backward
 @pytest.mark.parametrize("mode", ["none", "explicit", "noise", "noise_norm"])
 def test_gat_backward(dev, oracle, H, F, mode):
     """stag_gat_bwd against its CPU twin (oracle.gat_bwd = stag_gat_bwd_cpu, float64; pinned by the reference's own
@@ -1179,7 +1179,10 @@ def test_sage_pool_and_max_reducer(dev):
 # ---- amortised per-edge parameters with narrow heads (csrc/amort.hip) ----------------------------------------
 
 @pytest.mark.parametrize("n,K,C", [(0, 8, 2), (1, 1, 1), (1000, 9, 2), (5000, 128, 2), (3000, 50, 4), (2000, 256, 8),
-                                   (700, 1433, 16), (40000, 128, 3)])
+                                   (700, 1433, 16), (40000, 128, 3),
+                                   # the other (lanes per row, column tile) pairs: K <= 32, 64, 128, more; C <= 2, 4, 8, 16
+                                   (500, 20, 4), (500, 32, 8), (500, 40, 2), (500, 64, 8), (500, 50, 16), (500, 100, 8),
+                                   (500, 128, 16), (500, 300, 2), (500, 300, 4)])
 def test_node_project(dev, n, K, C):
     """stag_node_project_fwd / _bwd: y = x w + b, and (dx, dw, db) from one pass, against float64 torch."""
     from stag_amd import ops
@@ -1309,7 +1312,8 @@ def test_narrow_amortized_distribution_equals_dense_dataflow(dev, hidden):
 
 
 @pytest.mark.parametrize("n,H,F", [(1, 1, 4), (1000, 8, 32), (777, 3, 32), (500, 4, 64), (300, 2, 256), (2000, 16, 8),
-                                   (900, 1, 128), (1200, 8, 40), (640, 5, 12), (333, 3, 124), (50, 1, 252)])
+                                   (900, 1, 128), (1200, 8, 40), (640, 5, 12), (333, 3, 124), (50, 1, 252),
+                                   (400, 2, 32)])                # (2, 32): 16 lanes per row
 def test_head_dot(dev, n, H, F):
     """stag_head_dot_fwd / _bwd: GAT's el / er = (ft * attn).sum(-1) (stag/zoo/gat.py:109-110) and the gradients
     to ft, attn_l, attn_r against float64 torch."""

@@ -244,7 +244,7 @@ def test_csr_bit_exact(dev, oracle):
     assert np.array_equal(g.csr.eid.cpu().numpy()[t.nidx.cpu().numpy()], t.eid.cpu().numpy())
 
 
-@pytest.mark.parametrize("dn", [1, 5, 16, 128, 130])
+@pytest.mark.parametrize("dn", [1, 5, 16, 32, 64, 128, 130])      # 32, 64: 8 and 16 lanes per position
 def test_uniform_and_bernoulli_draws_bit_exact(dev, oracle, dn):
     g = random_graph(64, 700, seed=dn, hub=90, device=dev)
     og = oracle_graph(oracle, g)
@@ -567,11 +567,12 @@ def test_segment_reduce(dev, oracle):
     rng = np.random.default_rng(0)
     sizes = np.array([3, 0, 17, 1, 40, 5])
     offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-    x = rng.standard_normal((int(sizes.sum()), 37)).astype(np.float32)
-    for red in ("sum", "mean"):
-        got = ops.segment_reduce(torch.from_numpy(x).to(dev), torch.from_numpy(offs).to(dev), red)
-        ref = oracle.segment_reduce(x, offs, oracle.REDUCE_MEAN if red == "mean" else oracle.REDUCE_SUM)
-        assert_close(got, ref, what=f"segment {red}")
+    for D in (37, 4, 8, 16, 128, 256):                   # 16 lanes per row, then 1, 2, 4, 32, 64 (24 below: 8)
+        x = rng.standard_normal((int(sizes.sum()), D)).astype(np.float32)
+        for red in ("sum", "mean"):
+            got = ops.segment_reduce(torch.from_numpy(x).to(dev), torch.from_numpy(offs).to(dev), red)
+            ref = oracle.segment_reduce(x, offs, oracle.REDUCE_MEAN if red == "mean" else oracle.REDUCE_SUM)
+            assert_close(got, ref, what=f"segment {red} D={D}")
     # long segments (average > 256 rows) take the chunked two-stage form; a long, an empty, a
     # short and a chunk-aligned segment side by side, with the gradient
     sizes = np.array([4000, 0, 10, 512, 478])
@@ -587,7 +588,8 @@ def test_segment_reduce(dev, oracle):
         assert np.allclose(xd.grad.cpu().numpy(), want[:, None], rtol=1e-6)
 
 
-@pytest.mark.parametrize("H,F", [(3, 4), (8, 32), (4, 5), (1, 64), (4, 64), (2, 6)])
+@pytest.mark.parametrize("H,F", [(3, 4), (8, 32), (4, 5), (1, 64), (4, 64), (2, 6),
+                                 (4, 10), (8, 9)])      # F % 4 != 0, 10 and 18 chunks: gat_fwd_kernel<16>, <32>
 @pytest.mark.parametrize("kind", ["none", "explicit", "normal", "bernoulli"])
 def test_gat_fwd_vs_oracle(dev, oracle, H, F, kind):
     from stag_amd import ops
@@ -786,7 +788,7 @@ def test_fuzz_gat_against_oracle_and_composed_backward(dev, oracle):
 
 
 @pytest.mark.parametrize("kind,relu,logs", [("normal", False, False), ("normal", True, True), ("uniform", True, False)])
-@pytest.mark.parametrize("D", [1, 4, 12, 50, 100, 128, 256])
+@pytest.mark.parametrize("D", [1, 4, 8, 12, 32, 50, 100, 128, 256])      # 8, 32: 2 and 8 lanes per row
 def test_agg_bwd_edge_one_pass(dev, oracle, kind, relu, logs, D):
     """stag_agg_bwd_edge: dx and the gradients of [E, 1] parameters from ONE pass over the source-major CSR
     against the two-kernel statement (stag_agg_bwd for dx: bit for bit; stag_agg_bwd_w with reduce_k for the
@@ -831,6 +833,14 @@ def test_agg_bwd_edge_one_pass(dev, oracle, kind, relu, logs, D):
         ref = oracle.agg_bwd_w(og, x, gout * gs[:, None], src_scale=rs, spec=ospec).astype(np.float64).sum(1, keepdims=True)
         sc = max(1.0, float(np.abs(ref).max()))
         assert_close(got / sc, ref / sc, what=f"deriv {deriv} vs oracle")
+        if deriv == 1:   # stag_agg_bwd_w with one derivative of the spec (agg_bwd_w_kernel1) at this width
+            spec.deriv = 1
+            w1 = ops._bwd_w_raw(g.csr, xd, gg, D, rsd, spec=spec, reduce_k=True, seg_len=32)
+            spec.deriv = 0
+            assert_close(w1 / sc, ref / sc, what="stag_agg_bwd_w, one derivative, vs oracle")
+    # ... and without a spec (agg_bwd_w_kernel0): the [E, D] gradient of explicit weights
+    dw = ops._bwd_w_raw(g.csr, xd, gg, D, rsd, seg_len=32)
+    assert_close(dw, oracle.agg_bwd_w(og, x, gout * gs[:, None], src_scale=rs), what="stag_agg_bwd_w, no spec, vs oracle")
     # wider than one channel tile: no one-pass form
     assert ops._agg_bwd_edge_raw(g.csr_t, gd, xd, 300, spec, gsd, rsd, 32) is None
 

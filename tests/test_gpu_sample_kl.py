@@ -89,7 +89,7 @@ def shared_draw(graphs, name, dn):
 
 
 @pytest.mark.parametrize("gname", ["hub", "one"])
-@pytest.mark.parametrize("dn", [1, 4, 6, 8])
+@pytest.mark.parametrize("dn", [1, 4, 6, 8, 16, 32, 64, 128])      # 16 ... 128: 4, 8, 16 and 32 lanes per position
 @pytest.mark.parametrize("relu", [False, True])
 @pytest.mark.parametrize("mode", ["scalar", "per_channel", "per_edge1"])
 def test_value_and_gradients_over_the_sweep(dev, graphs, mode, relu, dn, gname):

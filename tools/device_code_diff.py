@@ -7,7 +7,9 @@ Every .hip of the Makefile's SRCS is compiled in both trees with the Makefile's 
 `--cuda-device-only -S -Rpass-analysis=kernel-resource-usage`.  Each .s is split into its functions (`.type <sym>,@function`
 up to `.end_amdhsa_kernel`) and compared function by function, by name, and so are the resource lines of each kernel.
 Left aside: lines naming `__hip_cuid_` (a hash of the source text) and the numbers in local labels (.LBB<n>_<m>,
-.Lfunc_end<n>, .Ltmp<n>: <n> counts functions or labels in emission order, which moves when a template is reordered).
+.Lfunc_end<n>, .Ltmp<n>: <n> counts functions or labels in emission order, which moves when a template is reordered or
+a launch site instantiates its kernels in another order), the same <n> where a loop note names a block (`; in Loop:
+Header=BB<n>_<m>`, `; Child Loop BB<n>_<m>`) and the padding in front of a comment, whose column moves with the width of <n>.
 --rename rewrites mangled-name fragments of PARENT_TREE's output (all pairs in one pass) for a refactor that renames
 kernels.  The texts are hashed and compared; nothing in them is interpreted.  Exit status 1 when anything differs."""
 import argparse
@@ -54,7 +56,8 @@ def functions(asm):
             return
         tmp = {}
         text = "\n".join(body)
-        text = re.sub(r"\.LBB\d+_(\d+)", r".LBB#_\1", text)
+        text = re.sub(r"(\.L|\b)BB\d+_(\d+)", r"\1BB#_\2", text)
+        text = re.sub(r"[ \t]+;", " ;", text)
         text = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1#", text)
         text = re.sub(r"\.Ltmp\d+", lambda m: ".Ltmp#%d" % tmp.setdefault(m.group(0), len(tmp)), text)
         out[cur] = hashlib.sha256(text.encode()).hexdigest()
