@@ -497,6 +497,36 @@ int stag_agg_fwd_half(const stag_csr* csr, const stag_plan* plan, const void* x,
                       int32_t D, const stag_noise_spec* spec, int32_t reduce, const float* src_scale,
                       const float* dst_scale, float* out, int64_t ldo, void* stream);
 
+/* ---- one weight per edge, shared by all channels (base_layer.sample_dimension = 1: DropEdge with a Bernoulli q_a, one
+ * learned weight per edge with an AmortizedDistribution(in, 1)), additive in v19 ----
+ * stag_agg_fwd with a weight of width 1 that every channel of the edge's message is multiplied by:
+ *     out[v, k] = dscale[v] * (sum | mean)_{p in row v} w1[p] * sscale[u_p] * x[u_p, k]
+ *   w1[p], for the edge at CSR position p with P = spec.pos_base + (csr.nidx ? csr.nidx[p] : p): element 0 of the noise
+ *   stream's block at (P, chunk 0) through the spec's parameters, relu and p1_log — bit for bit what
+ *   stag_noise_materialize writes for the same spec at Dn = 1 (so the same call on csr_t with nidx redraws the forward's
+ *   weights).  Kinds: EXPLICIT (p0 = w[E] by edge id, stride 1; group 0, 1 or D) and NORMAL | UNIFORM | BERNOULLI with
+ *   SCALAR parameters, PER_CHANNEL parameters (one-element rows) or PER_EDGE1 parameters ([E, 1] by edge id, p1_log
+ *   honoured); optional relu on every kind.  One Philox block per EDGE, drawn by one lane.
+ *   AN EDGE WHOSE WEIGHT IS EXACTLY 0.0 IS ABSENT: ITS ROW IS NOT READ (a dropped Bernoulli edge, a relu'd non-positive
+ *   draw, an explicit zero).  On finite x this changes no bit: sums run over blocks of 4 consecutive positions that start
+ *   at +0, and fma(0, x, t) = t.  On a non-finite row it yields 0 where a multiply would yield NaN — DGL's DropEdge
+ *   behaviour, where the edge is removed.  `mean` divides by the row's structural in-degree, as stag_agg_fwd does, not
+ *   by the number of kept edges.
+ *   Any D >= 1 (D % 4 != 0: scalar row forms); channels past 256 go to further channel tiles.  dscale, sscale, reduce,
+ *   `plan` (may be NULL) as for stag_agg_fwd.  Segments of long rows leave fp32 partial sums in plan->workspace
+ *   (>= stag_plan_workspace_bytes(n_seg, D, 0)), added in segment order (Kahan-compensated, as the sums inside long units
+ *   are) by a second small launch: no atomics, results are run-to-run bit-identical.  seg_counters are not used;
+ *   plan->xcd_order is ignored (plan order), which changes no bit.
+ *   STAG_ENOSYS — the caller materialises the [E, 1] weights and calls stag_agg_fwd with EXPLICIT weights and
+ *   group = D: in_norm; ldx == 0 (a broadcast row); chunk_base != 0; a per-channel log-scale; a launch across a 2^32
+ *   boundary of the global position.  STAG_EINVAL: a NULL csr / x / spec / out; D <= 0; 0 < ldx < D; ldo < D; unknown
+ *   kind or reduce; kind NONE (stag_agg_fwd's); PER_EDGE parameters; deriv != 0; EXPLICIT with a NULL p0 or a group other
+ *   than 0, 1, D; the counter bounds of stag_agg_fwd; a plan without units.  STAG_ENOMEM: workspace too small.  Every
+ *   argument is checked before any device work.                                                                   */
+int stag_agg_fwd_w1(const stag_csr* csr, const stag_plan* plan, const float* x, int64_t ldx, int32_t D,
+                    const stag_noise_spec* spec, int32_t reduce, const float* src_scale,
+                    const float* dst_scale, float* out, int64_t ldo, void* stream);
+
 /* w[eid, k] for every edge of the shard: what the reference keeps in
  * `self._edge_weight_sample` (stag/layers.py:107). relu and in_norm applied.
  * plan (may be NULL): the units bound what one team walks, so a hub row does not serialise.

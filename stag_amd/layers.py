@@ -142,6 +142,11 @@ class StagLayer(torch.nn.Module):
         if torch.is_grad_enabled() and self.norm and (live or feat.requires_grad):
             return None          # (in-norm's factor is differentiated by ops._AggregateVI / _Aggregate, per sample)
         dn = self._sample_dimension(feat)
+        from .zoo import GAT
+        if dn != feat.shape[-1] and not isinstance(self.base_layer, GAT):
+            # one weight per edge (base_layer.sample_dimension = 1) has no batched form: the loop.  (GAT's width is its
+            # number of heads, batched by ops.gat_aggregate_mc.)
+            return None
         gen = self._generator()
         # under autograd the batched forward shares the gathers and the backward is the loop's per-sample passes
         # (ops._AggregateMC); with fixed noise on an input that is data (every `*_mle` script) there is no backward at all

@@ -208,6 +208,28 @@ def _agg_half_raw(csrv, x, D, spec, reduce, src_scale, dst_scale, seg_len, plan_
     return out
 
 
+def _agg_w1_raw(csrv, x, D, spec, reduce, src_scale, dst_scale, seg_len, plan_t=None):
+    """One stag_agg_fwd_w1 launch on csrv: x [n_src, D] fp32 (unit column stride), spec of width 1 — an EdgeNoise's with
+    dn = 1, or EXPLICIT with p0 = w[E] — out [n_dst, D] fp32.  Bound through ctypes only; the plan is walked in plan
+    order.  On csr_t (nidx = forward positions) the same weights are redrawn: how the backward forms dx."""
+    spec = _targs_or_c(spec)
+    dev = _lib.require_device(x, csrv.indptr, src_scale, dst_scale)
+    out = torch.empty((csrv.n_dst, D), dtype=torch.float32, device=dev)
+    if csrv.n_dst == 0:
+        return out
+    if plan_t is None:
+        plan_t = csrv.plan(seg_len)
+    nbytes = _lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], D, 0) if plan_t is not None else 0
+    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t, width=None)
+    cs = csrv.struct()
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_agg_fwd_w1(
+            C.byref(cs), C.byref(plan_c) if plan_c is not None else None, _lib.ptr(x), x.stride(0), D, C.byref(spec),
+            reduce, _lib.ptr(src_scale), _lib.ptr(dst_scale), _lib.ptr(out), D, _lib.stream_of(dev))
+    _lib.check(rc, "stag_agg_fwd_w1")
+    return out
+
+
 def _targs_to_ctypes(t):
     """The torch-op argument tuple as a ctypes stag_noise_spec (for the entry points bound through ctypes)."""
     ni, nu, nf, p0, p1, epoch = t
@@ -1188,12 +1210,148 @@ def aggregate_into(csrv, x, out, weight, reduce, src_scale, dst_scale, plan_t):
     return out
 
 
+# ---- one weight per edge, shared by all channels (base_layer.sample_dimension = 1; an explicit [E] / [E, 1] weight) --------
+# stag_agg_fwd_w1 (one launch: the weight is drawn by one lane per edge and a row whose weight is exactly 0 is NOT READ) |
+# the two-launch route on the older kernels: EdgeNoise.materialize() at width 1, then stag_agg_fwd with EXPLICIT weights and
+# spec.group = D (the form GAT's d ft uses), the same on csr_t for dx.  The two-launch route MULTIPLIES by a zero weight
+# where the fused launch skips the row: on finite x the two agree to rounding, on a non-finite row whose edges are all
+# dropped the fused launch gives 0 and the two-launch route NaN.
+# False, by the usual rule — True only if the new launch is not slower than the route beside it, beyond the spread of two
+# repeats, for EVERY kind timed — because EXPLICIT weights miss it (profiles/r15/edge_weight.txt; us per call, fused against
+# two-launch, arxiv shape D = 128 | PPI batch D = 256; two repeats of the two-launch route differ by 0.1-0.6):
+#   Normal 113.9 / 178.9 | 126.7 / 172.9     Uniform 113.9 / 176.8 | 127.1 / 171.4     Bernoulli 0.9: 107.0 / 176.6 | 118.3 / 171.0
+#   Bernoulli 0.5: 79.1 / 176.4 | 74.9 / 170.2     Bernoulli 0.1: 62.2 / 174.7 | 50.5 / 170.0     EXPLICIT 130.8 / 119.0 | 139.3 / 116.3
+# Every drawn kind wins 44-120 us (no materialise launch, one Philox block per edge, dropped rows not gathered: Bernoulli(0.5)
+# runs below the 94.4 us of the launch without noise).  Dense explicit weights lose 12-23 us: a weight has to arrive
+# (eid, then w[eid]) before its row may be requested, where stag_agg_fwd requests the row and the weight together.
+# (The expanded [E, D] copy this replaces for tensors: 375.7 | 484.5 us.)  The skip itself costs nothing where nothing is
+# dropped: the same kernel built with -DSTAG_W1_NO_SKIP=1 reads 113.1 against 113.9 (Normal), 130.7 against 130.8 (EXPLICIT).
+EDGE_WEIGHT_FUSED = False
+EDGE_WEIGHT_TENSORS = True    # an explicit [E] / [E, 1] tensor takes the width-1 routes | is expanded to [E, D] first (A/B)
+
+
+def edge_weight_why_not(x, weight, graph, broadcast_x):
+    """The first reason ops.aggregate does not hand this call — x [N, D] with a weight of width 1: an EdgeNoise with
+    dn = 1, or a tensor [E] / [E, 1] — to stag_agg_fwd_w1 as it is, or None.  One clause per refusal of the entry point
+    (include/stag_hip.h) and per path without a form there.  A descriptor with in-norm or live parameters is
+    materialised first ([E, 1], differentiable) and asked about again as a tensor; everything else that gets a reason
+    takes the two-launch route (see EDGE_WEIGHT_FUSED)."""
+    if not EDGE_WEIGHT_FUSED:
+        return "switch"
+    if x.dim() != 2:
+        return "shape"
+    if broadcast_x or x.stride(0) == 0:
+        return "broadcast row"
+    if x.dtype != torch.float32:
+        return "dtype"
+    noise = weight if isinstance(weight, EdgeNoise) else None
+    if noise is not None:
+        if noise.dn != 1:
+            return "noise width"
+        if noise.kind < _lib.NOISE_NORMAL or noise.param_mode == _lib.PARAM_PER_EDGE:
+            return "noise parameters"
+        if noise.in_norm:
+            return "in-norm"
+        if noise.deriv:
+            return "derivative selector"
+        if noise.chunk_base:
+            return "channel shard"
+        if noise.n_samples != 1:
+            return "monte-carlo"
+        if noise.grad_params is not None and any(torch.is_tensor(p) and p.requires_grad for p in noise.grad_params):
+            return "parameter gradients"
+        if (noise.pos_base & 0xFFFFFFFF) + noise.graph.number_of_edges() > (1 << 32):
+            return "position range"
+    elif torch.is_tensor(weight):
+        if weight.dim() not in (1, 2) or (weight.dim() == 2 and weight.shape[1] != 1):
+            return "weight width"
+    else:
+        return "no weight"
+    if getattr(graph, "is_shard", False) or (noise is not None and getattr(noise.graph, "is_shard", False)):
+        return "shard"
+    if torch.compiler.is_compiling():
+        return "compiling"
+    if not x.is_cuda or (torch.is_tensor(weight) and not weight.is_cuda):
+        return "device"
+    return None
+
+
+def _w1_forward(csrv, x, D, noise, w1, fused, reduce, src_scale, dst_scale, seg_len, broadcast_x=False):
+    """One width-1 aggregation on csrv (csr: the forward; csr_t: dx): the fused launch on the descriptor or on explicit
+    w[E], or stag_agg_fwd on explicit [E, 1] weights with group = D (w1: the materialised weights of a descriptor)."""
+    if fused:
+        spec = _noise_spec(noise) if noise is not None else _explicit_spec(w1)
+        return _agg_w1_raw(csrv, x, D, spec, reduce, src_scale, dst_scale, seg_len)
+    return _agg_raw(csrv, x, D, _explicit_spec(w1, group=D), reduce, src_scale, dst_scale, seg_len,
+                    broadcast_x=broadcast_x)[0]
+
+
+class _AggregateW1(torch.autograd.Function):
+    """aggregate with one weight per edge under autograd: x and / or an explicit w [E, 1] carry gradients (a descriptor's
+    parameters do not: live ones arrive materialised).  dx is the forward's launch on csr_t with g (the fused launch
+    redraws the weights from the counters: nothing is saved); dw [E, 1] is stag_agg_bwd_w summed over the channels.
+    Nothing [E, D]-sized exists on either route."""
+
+    @staticmethod
+    def forward(ctx, x, w, graph, noise, reduce, src_scale, dst_scale, seg_len, broadcast_x):
+        fused = edge_weight_why_not(x, noise if noise is not None else w, graph, broadcast_x) is None
+        x = _f32c(x)
+        D = x.shape[1]
+        w1 = _f32c(w) if w is not None else (None if fused else noise.materialize())
+        out = _w1_forward(graph.csr, x, D, noise, w1, fused, reduce, src_scale, dst_scale, seg_len, broadcast_x)
+        ctx.graph, ctx.noise, ctx.reduce, ctx.seg_len = _owner(graph), noise, reduce, seg_len
+        ctx.broadcast_x, ctx.D, ctx.fused = broadcast_x, D, fused
+        need_x = w is not None and ctx.needs_input_grad[1]   # x is only read by dw
+        ctx.save_for_backward(x if need_x else None, w1, src_scale, dst_scale)     # (w1: E floats, or None)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, w1, src_scale, dst_scale = ctx.saved_tensors
+        graph, D = ctx.graph, ctx.D
+        g = _f32c(grad_out)
+        dvec = dst_scale
+        if ctx.reduce == _lib.REDUCE_MEAN:
+            inv = 1.0 / graph.csr.degrees.clamp(min=1).to(torch.float32)
+            dvec = inv if dvec is None else dvec * inv
+        dx = dw = None
+        if ctx.needs_input_grad[0] and not ctx.broadcast_x:
+            # dx[u,:] = ss[u] * sum_{p: src_p = u} w1[p] * dvec[v_p] * g[v_p,:]
+            dx = _w1_forward(graph.csr_t, g, D, ctx.noise, w1, ctx.fused, _lib.REDUCE_SUM, dvec, src_scale, ctx.seg_len)
+        if ctx.needs_input_grad[1]:
+            gg = g if dvec is None else g * dvec.unsqueeze(1)
+            dw = _bwd_w_raw(graph.csr, x, gg.contiguous(), D, src_scale, broadcast_x=ctx.broadcast_x, reduce_k=True,
+                            seg_len=ctx.seg_len)
+        return dx, dw, None, None, None, None, None, None, None
+
+
+def _aggregate_w1(graph, x, noise, w, reduce, src_scale, dst_scale, seg_len, broadcast_x):
+    """ops.aggregate with a weight of width 1 on rows of width D > 1 (noise: an EdgeNoise with dn = 1 | w: [E, 1])."""
+    if noise is not None:
+        if noise.n_samples > 1:
+            raise ValueError("Monte-Carlo batching does not apply to a noise width of 1: loop over the samples")
+        live = (noise.grad_params is not None and torch.is_grad_enabled()
+                and any(torch.is_tensor(p) and p.requires_grad for p in noise.grad_params))
+        if live or noise.in_norm:
+            # [E, 1]: the reparameterised sample (autograd reaches loc / log_scale through it), in-norm applied
+            w, noise = noise.materialize(), None
+    src_scale, dst_scale = _f32c(src_scale), _f32c(dst_scale)
+    if torch.is_grad_enabled() and (x.requires_grad or (w is not None and w.requires_grad)):
+        return _AggregateW1.apply(x, w, graph, noise, _REDUCE[reduce], src_scale, dst_scale, seg_len, broadcast_x)
+    fused = edge_weight_why_not(x, noise if noise is not None else w, graph, broadcast_x) is None
+    x = _f32c(x)
+    w1 = _f32c(w) if w is not None else (None if fused else noise.materialize())
+    return _w1_forward(graph.csr, x, x.shape[1], noise, w1, fused, _REDUCE[reduce], src_scale, dst_scale, seg_len,
+                       broadcast_x)
+
+
 def aggregate(graph, x, weight=None, reduce="sum", src_scale=None, dst_scale=None,
               seg_len=DEFAULT_SEG_LEN, _broadcast_x=False, _gathered=False):
     """out[v,:] = dscale[v] * sum|mean_{e=(u->v)} w[e,:] * sscale[u] * x[u,:]
 
     weight: None (plain copy_u), a tensor [E, D] indexed by edge id (explicit
-    `edge_weight`, stag/zoo/gcn.py:60-63), or an EdgeNoise (fused sampling).
+    `edge_weight`, stag/zoo/gcn.py:60-63), or an EdgeNoise (fused sampling).  A tensor [E] / [E, 1] or an
+    EdgeNoise of width 1 is one weight per edge shared by all channels (edge_weight_why_not): no [E, D] tensor.
     On a node-range shard (partition.GraphShard) x holds this rank's rows and the call includes
     the halo exchange."""
     if x.dim() != 2:
@@ -1211,8 +1369,12 @@ def aggregate(graph, x, weight=None, reduce="sum", src_scale=None, dst_scale=Non
         if w.dim() == 1:
             w = w.unsqueeze(1)
         if w.shape[1] != D:
+            if w.dim() == 2 and w.shape[1] == 1 and EDGE_WEIGHT_TENSORS:      # one weight per edge: no [E, D] copy
+                return _aggregate_w1(graph, x, None, w, reduce, src_scale, dst_scale, seg_len, _broadcast_x)
             w = w.expand(w.shape[0], D)
     if noise is not None and noise.dn != D:
+        if noise.dn == 1:          # base_layer.sample_dimension = 1: one weight per edge, shared by all channels
+            return _aggregate_w1(graph, x, noise, None, reduce, src_scale, dst_scale, seg_len, _broadcast_x)
         raise ValueError(f"noise width {noise.dn} != feature width {D}")
     if noise is not None and noise.n_samples > 1:
         if _broadcast_x:
@@ -1448,7 +1610,11 @@ def aggregate_max(graph, x, weight=None, seg_len=DEFAULT_SEG_LEN, _broadcast_x=F
         if w.dim() == 1:
             w = w.unsqueeze(1)
     if noise is not None and noise.dn != D:
-        raise ValueError(f"noise width {noise.dn} != feature width {D}")
+        if noise.dn != 1:
+            raise ValueError(f"noise width {noise.dn} != feature width {D}")
+        # one weight per edge: the [E, 1] tensor (differentiable with live parameters), then the tensor path below
+        weight = w = noise.materialize()
+        noise = None
     grad_on = torch.is_grad_enabled()
     live = (noise is not None and noise.grad_params is not None and grad_on
             and any(torch.is_tensor(p) and p.requires_grad for p in noise.grad_params))
