@@ -9,15 +9,10 @@
 // draws the two Philox blocks its channels belong to (chunks chunk_base + 2c and + 2c + 1 of include/stag_hip.h's
 // noise stream: the same w[e, k] bits as an fp32 launch with the same spec).  A row takes D / 8 lanes, a team is the
 // next power of two of that (8 ... 64 lanes); channels past 512 go to further channel tiles (blockIdx.y).
-// The launch walks the plan's units in plan order (one team per unit; no plan: one unit per row).  Edges are taken in
-// blocks (2 with a draw, 4 without), a block's terms are summed from zero and folded into the unit's sum in order,
-// Kahan-compensated once the unit is longer than 16 edges (AggTeam::fold_into's rule).  A segment of a long row
-// leaves its fp32 partial in the plan's workspace; a second small launch (one workgroup per long row) adds every long
-// row's partials — Kahan sums of groups of 16 in segment order, then of the group sums in group order — and applies
-// the row scale.  No atomics, no arrival counters: two launches with the same inputs give the same bits.  agg_kernel / agg_plain_kernel are not touched: they are tuned to the VGPR.
+// How the plan's units are walked, a block sum is folded and a long row's segments are merged: unit_sum.hpp.  Edges are
+// taken in blocks (2 with a draw, 4 without).  agg_kernel / agg_plain_kernel are not touched: they are tuned to the VGPR.
 #include "agg_half.hpp"
-#include "entry_args.hpp"
-#include "agg_kernel.hpp"   // load4 / store4, kKahanMinLen, u32x4_t (read-only helpers)
+#include "unit_sum.hpp"     // the unit walk, the row scale, the N-wide store; agg_kernel.hpp's load4, u32x4_t
 
 namespace stag {
 namespace {
@@ -45,45 +40,13 @@ __device__ __forceinline__ void widen8(const u32x4_t t, float (&v)[8]) {
   }
 }
 
-__device__ __forceinline__ void store8(float* p, int k0, int D, bool vec, const float (&v)[8]) {
-  const float lo[4] = {v[0], v[1], v[2], v[3]}, hi[4] = {v[4], v[5], v[6], v[7]};
-  store4(p, k0, D, vec, lo);
-  store4(p, k0 + 4, D, vec, hi);
-}
-
-// the unit a team serves (plan order; no plan: unit i = row i); false past the end
-template <int LPE>
-__device__ __forceinline__ bool half_unit(const HalfArgs& a, int& row, int& start, int& len, int& slot) {
-  const int64_t rec = (int64_t)blockIdx.x * (256 / LPE) + threadIdx.x / LPE;
-  if (rec >= a.n_units) return false;
-  if (a.units) {
-    const int4 q = *reinterpret_cast<const int4*>(a.units + rec);
-    slot = q.w;
-    row = slot >= 0 ? a.long_rows[q.x] : q.x;
-    start = q.y;
-    len = q.z;
-  } else {
-    row = (int)rec;
-    start = a.indptr[row];
-    len = a.indptr[row + 1] - start;
-    slot = -1;
-  }
-  return true;
-}
-
-__device__ __forceinline__ float row_scale(const HalfArgs& a, int v, int deg) {
-  float dv = a.dst_scale ? a.dst_scale[v] : 1.0f;
-  if (a.mean) dv *= __builtin_amdgcn_rcpf((float)(deg > 1 ? deg : 1));
-  return dv;
-}
-
 template <int KIND, int DT, int LPE>
 __global__ __launch_bounds__(256) void agg_half_fwd_kernel(const HalfArgs a) {
   constexpr int BLK = half_blk<KIND>();
   const int c = blockIdx.y * LPE + threadIdx.x % LPE;   // the lane's group of 8 channels
   const int k0 = 8 * c;
   int row, start, len, slot;
-  if (k0 >= a.D || !half_unit<LPE>(a, row, start, len, slot)) return;
+  if (k0 >= a.D || !unit_of<LPE>(a, row, start, len, slot)) return;
   const PhiloxKey key = resolve_epoch(a.key);
   const uint32_t koff = (uint32_t)k0 * 2u;
   const bool narrow = a.x_bytes != 0;
@@ -161,6 +124,7 @@ __global__ __launch_bounds__(256) void agg_half_fwd_kernel(const HalfArgs a) {
         }
       }
     }
+    // fold_block<8> (unit_sum.hpp), written out: through the helper this kernel's instructions move
     if (kahan) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
@@ -175,21 +139,17 @@ __global__ __launch_bounds__(256) void agg_half_fwd_kernel(const HalfArgs a) {
     }
   }
   if (slot >= 0) {   // a segment: its partial, added by agg_half_merge_kernel
-    store8(a.ws + (int64_t)slot * a.D, k0, a.D, a.ovec != 0, acc);
+    store_n(a.ws + (int64_t)slot * a.D, k0, a.D, a.ovec != 0, acc);
     return;
   }
   const float dv = row_scale(a, row, len);
 #pragma unroll
   for (int q = 0; q < 8; ++q) acc[q] *= dv;
-  store8(a.out + (int64_t)row * a.ldo, k0, a.D, a.ovec != 0, acc);
+  store_n(a.out + (int64_t)row * a.ldo, k0, a.D, a.ovec != 0, acc);
 }
 
-// One workgroup per long row (a hub row has hundreds of segments: one team adding them one after the other is a chain
-// of dependent loads — 39 us for the 13,000-edge hub of the arxiv-shaped graph).  The two-level form of
-// two_level_sum (agg_kernel.hpp): Kahan sums of GROUPS of kCombineGroup partials in segment order, one group per team
-// and round, then team 0 folds the group sums in group order — a group's Kahan residual joins the second level's
-// compensation.  Groups are cut by segment index alone, so the arithmetic does not depend on the teams per workgroup
-// (the row's width), only on the row's segments.
+// seg_merge<8, LPE> (unit_sum.hpp), written out: through the template the call at seg_len = 16 on the arxiv-shaped graph
+// (four rounds of the merge) measured 0.17 us slower than this body, the parent's own spread being 0.03 (profiles/r16)
 template <int LPE>
 __global__ __launch_bounds__(256) void agg_half_merge_kernel(const HalfArgs a) {
   constexpr int T = 256 / LPE, kAhead = 8;
@@ -255,7 +215,7 @@ __global__ __launch_bounds__(256) void agg_half_merge_kernel(const HalfArgs a) {
   const float dv = row_scale(a, row, a.indptr[row + 1] - a.indptr[row]);
 #pragma unroll
   for (int q = 0; q < 8; ++q) sum[q] = (sum[q] - comp[q]) * dv;
-  store8(a.out + (int64_t)row * a.ldo, k0, a.D, vec, sum);
+  store_n(a.out + (int64_t)row * a.ldo, k0, a.D, vec, sum);
 }
 
 template <int KIND>
@@ -270,25 +230,15 @@ void half_fwd_kind(const HalfArgs& a, int dtype, int lpe, dim3 grid, hipStream_t
 }  // namespace
 
 hipError_t half_fwd_launch(const HalfArgs& a, int kind, int dtype, int32_t n_seg, hipStream_t s) {
-  const int lpe = lanes_for(a.D / 8, 8);   // 8 channels per lane
-  const int T = 256 / lpe;
-  const int tiles = (a.D / 8 + lpe - 1) / lpe;
-  const dim3 grid((unsigned)(((int64_t)a.n_units + T - 1) / T), tiles);
-  if (grid.x > 0) {
-    switch (kind) {
-      case kNone: half_fwd_kind<kNone>(a, dtype, lpe, grid, s); break;
-      case kNormal: half_fwd_kind<kNormal>(a, dtype, lpe, grid, s); break;
-      case kUniform: half_fwd_kind<kUniform>(a, dtype, lpe, grid, s); break;
-      default: half_fwd_kind<kBernoulli>(a, dtype, lpe, grid, s); break;
-    }
-  }
-  if (n_seg > 0 && a.n_long > 0) {
-    const dim3 mg(a.n_long, tiles);                      // one workgroup per long row and channel tile
-    pick<64, 32, 16, 8>(lpe, [&](auto L) {
-      hipLaunchKernelGGL((agg_half_merge_kernel<decltype(L)::value>), mg, dim3(256), 0, s, a);
-    });
-  }
-  return hipGetLastError();
+  return unit_sum_launch(a.D, 8, 8, a.n_units, a.n_long, n_seg,
+      [&](int lpe, dim3 grid) {
+        pick<kNone, kNormal, kUniform, kBernoulli>(kind, [&](auto K) { half_fwd_kind<decltype(K)::value>(a, dtype, lpe, grid, s); });
+      },
+      [&](int lpe, dim3 grid) {
+        pick<64, 32, 16, 8>(lpe, [&](auto L) {
+          hipLaunchKernelGGL((agg_half_merge_kernel<decltype(L)::value>), grid, dim3(256), 0, s, a);
+        });
+      });
 }
 
 }  // namespace stag
@@ -332,13 +282,7 @@ extern "C" int stag_agg_fwd_half(const stag_csr* csr, const stag_plan* plan, con
   a.indptr = csr->indptr; a.indices = csr->indices; a.nidx = csr->nidx;   // (csr->eid: nothing here is indexed by edge id)
   a.n_rows = csr->n_dst; a.D = D;
   a.x = x; a.ldxb = (uint32_t)(ldx * 2);
-  {
-    // 32-bit byte offsets and 24-bit multiplies behind a buffer descriptor when they reach every row, else 64-bit addresses
-    const uint64_t xbytes = csr->n_src > 0 ? ((uint64_t)(csr->n_src - 1) * (uint64_t)ldx + (uint64_t)D) * 2u : 0u;
-    const bool narrow = xbytes > 0 && xbytes < (1ull << 32) && csr->n_src < (1 << 24) && (uint64_t)ldx * 2u < (1u << 24);
-    a.x_bytes = narrow ? (uint32_t)xbytes : 0u;
-    if (!narrow && (uint64_t)ldx * 2u >= (1ull << 32)) return STAG_ENOSYS;   // a row stride past 32 bits of bytes
-  }
+  if ((rc = narrow_rows(csr->n_src, ldx, D, 2, a.x_bytes))) return rc;
   fill_spec(a, spec, 0);   // (flags: relu only; a derivative and a log-scale were refused above)
   a.src_scale = src_scale; a.dst_scale = dst_scale; a.mean = reduce == STAG_REDUCE_MEAN;
   fill_plan(a, csr, plan);   // plan->xcd_order is ignored: the units are walked in plan order

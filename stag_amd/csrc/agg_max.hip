@@ -408,15 +408,8 @@ hipError_t max_fwd_launch(const MaxArgs& a, int32_t n_seg, hipStream_t s) {
   const bool vec = a.D % 4 == 0 && a.ldx % 4 == 0 && a.ldo % 4 == 0 && aligned16(a.x) && aligned16(a.out) &&
                    (n_seg == 0 || aligned16(a.ws));
   const dim3 grid = unit_grid(a, lpe);
-  if (grid.x > 0) {
-    switch (a.kind) {
-      case kNone: fwd_kind<kNone>(a, lpe, vec, grid, s); break;
-      case kExplicit: fwd_kind<kExplicit>(a, lpe, vec, grid, s); break;
-      case kNormal: fwd_kind<kNormal>(a, lpe, vec, grid, s); break;
-      case kUniform: fwd_kind<kUniform>(a, lpe, vec, grid, s); break;
-      default: fwd_kind<kBernoulli>(a, lpe, vec, grid, s); break;
-    }
-  }
+  if (grid.x > 0)
+    pick<kNone, kExplicit, kNormal, kUniform, kBernoulli>(a.kind, [&](auto K) { fwd_kind<decltype(K)::value>(a, lpe, vec, grid, s); });
   if (n_seg > 0 && a.n_long > 0) {
     const int T = 256 / lpe;
     const dim3 mg((a.n_long + T - 1) / T, grid.y);
@@ -438,19 +431,12 @@ hipError_t max_bwd_launch(const MaxArgs& a, int32_t n_seg, hipStream_t s) {
   const dim3 grid = unit_grid(a, lpe);
   const bool grad = a.dp0 != nullptr;
   if (grid.x > 0) {
-    switch (a.kind) {
-      case kNone: bwd_kind<kNone, 1>(a, lpe, vec, grid, s); break;
-      case kExplicit: bwd_kind<kExplicit, 1>(a, lpe, vec, grid, s); break;
-      case kNormal:
-        if (grad) bwd_kind<kNormal, 3>(a, lpe, vec, grid, s);
-        else bwd_kind<kNormal, 1>(a, lpe, vec, grid, s);
-        break;
-      case kUniform:
-        if (grad) bwd_kind<kUniform, 3>(a, lpe, vec, grid, s);
-        else bwd_kind<kUniform, 1>(a, lpe, vec, grid, s);
-        break;
-      default: bwd_kind<kBernoulli, 1>(a, lpe, vec, grid, s); break;
-    }
+    pick<kNone, kExplicit, kNormal, kUniform, kBernoulli>(a.kind, [&](auto K) {
+      constexpr int KIND = decltype(K)::value;
+      constexpr bool reparam = KIND == kNormal || KIND == kUniform;   // the kinds with parameter gradients
+      if (reparam && grad) bwd_kind<KIND, reparam ? 3 : 1>(a, lpe, vec, grid, s);
+      else bwd_kind<KIND, 1>(a, lpe, vec, grid, s);
+    });
   }
   if (n_seg > 0 && a.n_long > 0) {
     const int T = 256 / lpe;

@@ -15,14 +15,10 @@
 //   consecutive edges of the round, kept or not; a block sum starts at +0 and fma(0, x, t) = t), which is why the kept
 //   edges are not compacted first: compaction would move the block boundaries with the draw.  On a non-finite row
 //   the skip yields 0 where a multiply would yield NaN: the edge is absent, as after DGL's DropEdge.
-// Block sums are folded into the unit's sum in order, Kahan-compensated once the unit is longer than kKahanMinLen
-// (AggTeam::fold_into's rule).  A segment of a long row leaves its fp32 partial in the plan's workspace; a second small
-// launch (one workgroup per long row) adds every long row's partials group by group in segment order and applies the
-// row scale.  No atomics, no arrival counters: two launches with the same inputs give the same bits.
+// How the plan's units are walked, a block sum is folded and a long row's segments are merged: unit_sum.hpp.
 // agg_kernel.hpp and noise.hpp are included for their helpers only.
 #include "agg_w1.hpp"
-#include "entry_args.hpp"
-#include "agg_kernel.hpp"   // load4 / store4, kKahanMinLen, kCombineGroup, u32x4_t (read-only helpers)
+#include "unit_sum.hpp"     // the unit walk, the block fold, the row scale, the segment merge; agg_kernel.hpp's load4, u32x4_t
 
 // A/B only (tools/ab_bench.py): 1 = multiply by a zero weight instead of skipping its row.  The contract is the skip.
 #ifndef STAG_W1_NO_SKIP
@@ -40,32 +36,6 @@ namespace {
 #endif
 template <int LPE>
 constexpr int w1_group() { return LPE >= 8 ? STAG_W1_GROUP : 4; }
-
-// the unit a team serves (plan order; no plan: unit i = row i); false past the end
-template <int LPE>
-__device__ __forceinline__ bool w1_unit(const W1Args& a, int& row, int& start, int& len, int& slot) {
-  const int64_t rec = (int64_t)blockIdx.x * (256 / LPE) + threadIdx.x / LPE;
-  if (rec >= a.n_units) return false;
-  if (a.units) {
-    const int4 q = *reinterpret_cast<const int4*>(a.units + rec);
-    slot = q.w;
-    row = slot >= 0 ? a.long_rows[q.x] : q.x;
-    start = q.y;
-    len = q.z;
-  } else {
-    row = (int)rec;
-    start = a.indptr[row];
-    len = a.indptr[row + 1] - start;
-    slot = -1;
-  }
-  return true;
-}
-
-__device__ __forceinline__ float w1_row_scale(const W1Args& a, int v, int deg) {
-  float dv = a.dst_scale ? a.dst_scale[v] : 1.0f;
-  if (a.mean) dv *= __builtin_amdgcn_rcpf((float)(deg > 1 ? deg : 1));
-  return dv;
-}
 
 // the weight of the edge at CSR position p: stag_noise_materialize's w[eid, 0] at Dn = 1, bit for bit
 template <int KIND>
@@ -101,7 +71,7 @@ __global__ __launch_bounds__(256) void agg_w1_fwd_kernel(const W1Args a) {
   // (no early return for a lane without channels: it still loads and draws the edges of its position in a round)
   const bool live = k0 < a.D;
   int row, start, len, slot;
-  if (!w1_unit<LPE>(a, row, start, len, slot)) return;
+  if (!unit_of<LPE>(a, row, start, len, slot)) return;
   PhiloxKey key{};
   if constexpr (KIND >= kNormal) key = resolve_epoch(a.key);
   const uint32_t koff = (uint32_t)k0 * 4u;
@@ -164,18 +134,7 @@ __global__ __launch_bounds__(256) void agg_w1_fwd_kernel(const W1Args a) {
           }
         }
         if (j0 + b < n) {                                // (a block past the round's end is not a block of the sum)
-          if (kahan) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const float y = t[c] - comp[c];
-              const float s = acc[c] + y;
-              comp[c] = (s - acc[c]) - y;
-              acc[c] = s;
-            }
-          } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[c] += t[c];
-          }
+          fold_block(kahan, t, acc, comp);
         }
       }
     }
@@ -185,73 +144,14 @@ __global__ __launch_bounds__(256) void agg_w1_fwd_kernel(const W1Args a) {
     store4(a.ws + (int64_t)slot * a.D, k0, a.D, a.ovec != 0, acc);
     return;
   }
-  const float dv = w1_row_scale(a, row, len);
+  const float dv = row_scale(a, row, len);
 #pragma unroll
   for (int c = 0; c < 4; ++c) acc[c] *= dv;
   store4(a.out + (int64_t)row * a.ldo, k0, a.D, a.ovec != 0, acc);
 }
 
-// One workgroup per long row and channel tile: Kahan sums of GROUPS of kCombineGroup partials in segment order, one
-// group per team and round, then team 0 folds the group sums in group order — a group's Kahan residual joins the
-// second level's compensation (the two-level form of agg_half_merge_kernel).  Groups are cut by segment index alone.
 template <int LPE>
-__global__ __launch_bounds__(256) void agg_w1_merge_kernel(const W1Args a) {
-  constexpr int T = 256 / LPE, kAhead = 8;
-  __shared__ float part[T][2][LPE * 4];          // a round's group sums and what they still owe (8 KB)
-  const int r = blockIdx.x, team = threadIdx.x / LPE, lane = threadIdx.x % LPE;
-  const int k0 = 4 * (blockIdx.y * LPE + lane);
-  const bool live = k0 < a.D;                    // (no early return: the workgroup meets at barriers)
-  const int row = a.long_rows[r];
-  const int s0 = a.long_seg_ptr[r], s1 = a.long_seg_ptr[r + 1];
-  const bool vec = a.ovec != 0;
-  float sum[4] = {0.f, 0.f, 0.f, 0.f}, comp[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int g0 = s0; g0 < s1; g0 += kCombineGroup * T) {   // uniform over the workgroup
-    const int gs = g0 + team * kCombineGroup;
-    if (live && gs < s1) {
-      const int ge = min(gs + kCombineGroup, s1);
-      float gsum[4] = {0.f, 0.f, 0.f, 0.f}, gres[4] = {0.f, 0.f, 0.f, 0.f};
-      for (int s = gs; s < ge; s += kAhead) {
-        float t[kAhead][4];
-#pragma unroll
-        for (int j = 0; j < kAhead; ++j)
-          if (s + j < ge) load4(a.ws + (int64_t)(s + j) * a.D, k0, a.D, vec, t[j]);
-#pragma unroll
-        for (int j = 0; j < kAhead; ++j) {
-          if (s + j < ge) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const float y = t[j][c] - gres[c];
-              const float n = gsum[c] + y;
-              gres[c] = (n - gsum[c]) - y;
-              gsum[c] = n;
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) { part[team][0][lane * 4 + c] = gsum[c]; part[team][1][lane * 4 + c] = gres[c]; }
-    }
-    __syncthreads();
-    if (team == 0 && live) {
-      for (int j = 0; j < T && g0 + j * kCombineGroup < s1; ++j) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          comp[c] += part[j][1][lane * 4 + c];             // true group sum = its sum - its residual
-          const float y = part[j][0][lane * 4 + c] - comp[c];
-          const float n = sum[c] + y;
-          comp[c] = (n - sum[c]) - y;
-          sum[c] = n;
-        }
-      }
-    }
-    __syncthreads();                                       // the next round overwrites the group sums
-  }
-  if (team != 0 || !live) return;
-  const float dv = w1_row_scale(a, row, a.indptr[row + 1] - a.indptr[row]);
-#pragma unroll
-  for (int c = 0; c < 4; ++c) sum[c] = (sum[c] - comp[c]) * dv;
-  store4(a.out + (int64_t)row * a.ldo, k0, a.D, vec, sum);
-}
+__global__ __launch_bounds__(256) void agg_w1_merge_kernel(const W1Args a) { seg_merge<4, LPE>(a); }
 
 template <int KIND>
 void w1_fwd_kind(const W1Args& a, int lpe, dim3 grid, hipStream_t s) {
@@ -263,26 +163,15 @@ void w1_fwd_kind(const W1Args& a, int lpe, dim3 grid, hipStream_t s) {
 }  // namespace
 
 hipError_t w1_fwd_launch(const W1Args& a, int kind, int32_t n_seg, hipStream_t s) {
-  const int nchunk = (a.D + 3) / 4;
-  const int lpe = lanes_for(nchunk, 4);   // 4 channels per lane
-  const int T = 256 / lpe;
-  const int tiles = (nchunk + lpe - 1) / lpe;
-  const dim3 grid((unsigned)(((int64_t)a.n_units + T - 1) / T), tiles);
-  if (grid.x > 0) {
-    switch (kind) {
-      case kExplicit: w1_fwd_kind<kExplicit>(a, lpe, grid, s); break;
-      case kNormal: w1_fwd_kind<kNormal>(a, lpe, grid, s); break;
-      case kUniform: w1_fwd_kind<kUniform>(a, lpe, grid, s); break;
-      default: w1_fwd_kind<kBernoulli>(a, lpe, grid, s); break;
-    }
-  }
-  if (n_seg > 0 && a.n_long > 0) {
-    const dim3 mg(a.n_long, tiles);                      // one workgroup per long row and channel tile
-    pick<64, 32, 16, 8, 4>(lpe, [&](auto L) {
-      hipLaunchKernelGGL((agg_w1_merge_kernel<decltype(L)::value>), mg, dim3(256), 0, s, a);
-    });
-  }
-  return hipGetLastError();
+  return unit_sum_launch(a.D, 4, 4, a.n_units, a.n_long, n_seg,
+      [&](int lpe, dim3 grid) {
+        pick<kExplicit, kNormal, kUniform, kBernoulli>(kind, [&](auto K) { w1_fwd_kind<decltype(K)::value>(a, lpe, grid, s); });
+      },
+      [&](int lpe, dim3 grid) {
+        pick<64, 32, 16, 8, 4>(lpe, [&](auto L) {
+          hipLaunchKernelGGL((agg_w1_merge_kernel<decltype(L)::value>), grid, dim3(256), 0, s, a);
+        });
+      });
 }
 
 }  // namespace stag
@@ -321,13 +210,7 @@ extern "C" int stag_agg_fwd_w1(const stag_csr* csr, const stag_plan* plan, const
   a.indptr = csr->indptr; a.indices = csr->indices; a.eid = csr->eid; a.nidx = csr->nidx;
   a.n_rows = csr->n_dst; a.D = D;
   a.x = x; a.ldxb = (uint32_t)(ldx * 4);
-  {
-    // 32-bit byte offsets and 24-bit multiplies behind a buffer descriptor when they reach every row, else 64-bit addresses
-    const uint64_t xbytes = csr->n_src > 0 ? ((uint64_t)(csr->n_src - 1) * (uint64_t)ldx + (uint64_t)D) * 4u : 0u;
-    const bool narrow = xbytes > 0 && xbytes < (1ull << 32) && csr->n_src < (1 << 24) && (uint64_t)ldx * 4u < (1u << 24);
-    a.x_bytes = narrow ? (uint32_t)xbytes : 0u;
-    if (!narrow && (uint64_t)ldx * 4u >= (1ull << 32)) return STAG_ENOSYS;   // a row stride past 32 bits of bytes
-  }
+  if ((rc = narrow_rows(csr->n_src, ldx, D, 4, a.x_bytes))) return rc;
   a.xvec = D % 4 == 0 && ldx % 4 == 0 && aligned16(x);
   fill_spec(a, spec, 0);   // (flags: relu and the log-scale; a derivative was refused above)
   a.src_scale = src_scale; a.dst_scale = dst_scale; a.mean = reduce == STAG_REDUCE_MEAN;

@@ -15,6 +15,18 @@ namespace stag {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// How a kernel addresses n_src gathered rows of D elements of esize bytes, ldx elements apart.  x_bytes = the extent of
+// x when 32-bit byte offsets and 24-bit multiplies (row < 2^24, stride < 2^24 bytes) reach all of it behind a buffer
+// descriptor, else 0: 64-bit addresses, whose 32-bit row stride refuses one past 32 bits of bytes (STAG_ENOSYS).
+// (gat.hip's narrow_extent is another rule: contiguous rows, no stride limit.)
+inline int narrow_rows(int64_t n_src, int64_t ldx, int32_t D, uint32_t esize, uint32_t& x_bytes) {
+  const uint64_t stride = (uint64_t)ldx * esize;
+  const uint64_t xbytes = n_src > 0 ? ((uint64_t)(n_src - 1) * (uint64_t)ldx + (uint64_t)D) * esize : 0u;
+  const bool narrow = xbytes > 0 && xbytes < (1ull << 32) && n_src < (1 << 24) && stride < (1u << 24);
+  x_bytes = narrow ? (uint32_t)xbytes : 0u;
+  return !narrow && stride >= (1ull << 32) ? STAG_ENOSYS : STAG_OK;
+}
+
 // lanes per row: the smallest power of two >= min_lanes that covers nchunk chunks, capped at a wave
 inline int lanes_for(int nchunk, int min_lanes) {
   int lpe = min_lanes;

@@ -186,9 +186,9 @@ def _agg_raw(csrv, x, D, spec, reduce, src_scale, dst_scale, seg_len, want_norm_
 _HALF_DTYPES = {torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 
 
-def _agg_half_raw(csrv, x, D, spec, reduce, src_scale, dst_scale, seg_len, plan_t=None):
-    """One stag_agg_fwd_half launch on csrv: x [n_src, D] fp16 | bf16 as it is (unit column stride, any row stride the
-    entry point takes), out [n_dst, D] fp32.  Bound through ctypes only; the plan is walked in plan order."""
+def _unit_sum_raw(entry, csrv, x, x_args, D, spec, reduce, src_scale, dst_scale, seg_len, plan_t):
+    """One launch of a plan-order sum entry point (stag_agg_fwd_half | stag_agg_fwd_w1) on csrv: out [n_dst, D] fp32.
+    x_args(): what the entry point takes between x and D.  Bound through ctypes only; the plan is walked in plan order."""
     spec = _targs_or_c(spec)
     dev = _lib.require_device(x, csrv.indptr, src_scale, dst_scale)
     out = torch.empty((csrv.n_dst, D), dtype=torch.float32, device=dev)
@@ -200,34 +200,24 @@ def _agg_half_raw(csrv, x, D, spec, reduce, src_scale, dst_scale, seg_len, plan_
     plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t, width=None)
     cs = csrv.struct()
     with _lib.on_device(dev):
-        rc = _lib.lib().stag_agg_fwd_half(
-            C.byref(cs), C.byref(plan_c) if plan_c is not None else None, _lib.ptr(x), _HALF_DTYPES[x.dtype],
-            x.stride(0), D, C.byref(spec), reduce, _lib.ptr(src_scale), _lib.ptr(dst_scale), _lib.ptr(out), D,
-            _lib.stream_of(dev))
-    _lib.check(rc, "stag_agg_fwd_half")
+        rc = getattr(_lib.lib(), entry)(
+            C.byref(cs), C.byref(plan_c) if plan_c is not None else None, _lib.ptr(x), *x_args(), D, C.byref(spec),
+            reduce, _lib.ptr(src_scale), _lib.ptr(dst_scale), _lib.ptr(out), D, _lib.stream_of(dev))
+    _lib.check(rc, entry)
     return out
+
+
+def _agg_half_raw(csrv, x, D, spec, reduce, src_scale, dst_scale, seg_len, plan_t=None):
+    """stag_agg_fwd_half: x [n_src, D] fp16 | bf16 as it is (unit column stride, any row stride the entry point takes)."""
+    return _unit_sum_raw("stag_agg_fwd_half", csrv, x, lambda: (_HALF_DTYPES[x.dtype], x.stride(0)), D, spec, reduce,
+                         src_scale, dst_scale, seg_len, plan_t)
 
 
 def _agg_w1_raw(csrv, x, D, spec, reduce, src_scale, dst_scale, seg_len, plan_t=None):
-    """One stag_agg_fwd_w1 launch on csrv: x [n_src, D] fp32 (unit column stride), spec of width 1 — an EdgeNoise's with
-    dn = 1, or EXPLICIT with p0 = w[E] — out [n_dst, D] fp32.  Bound through ctypes only; the plan is walked in plan
-    order.  On csr_t (nidx = forward positions) the same weights are redrawn: how the backward forms dx."""
-    spec = _targs_or_c(spec)
-    dev = _lib.require_device(x, csrv.indptr, src_scale, dst_scale)
-    out = torch.empty((csrv.n_dst, D), dtype=torch.float32, device=dev)
-    if csrv.n_dst == 0:
-        return out
-    if plan_t is None:
-        plan_t = csrv.plan(seg_len)
-    nbytes = _lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], D, 0) if plan_t is not None else 0
-    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t, width=None)
-    cs = csrv.struct()
-    with _lib.on_device(dev):
-        rc = _lib.lib().stag_agg_fwd_w1(
-            C.byref(cs), C.byref(plan_c) if plan_c is not None else None, _lib.ptr(x), x.stride(0), D, C.byref(spec),
-            reduce, _lib.ptr(src_scale), _lib.ptr(dst_scale), _lib.ptr(out), D, _lib.stream_of(dev))
-    _lib.check(rc, "stag_agg_fwd_w1")
-    return out
+    """stag_agg_fwd_w1: x [n_src, D] fp32 (unit column stride), spec of width 1 — an EdgeNoise's with dn = 1, or EXPLICIT
+    with p0 = w[E].  On csr_t (nidx = forward positions) the same weights are redrawn: how the backward forms dx."""
+    return _unit_sum_raw("stag_agg_fwd_w1", csrv, x, lambda: (x.stride(0),), D, spec, reduce, src_scale, dst_scale, seg_len,
+                         plan_t)
 
 
 def _targs_to_ctypes(t):

@@ -198,6 +198,41 @@ def test_plan_forms_and_determinism(dev, oracle, dname, D):
         assert torch.equal(xo.view(torch.int32), outs[seg_len].view(torch.int32)), "xcd_order changes no bit"
 
 
+@pytest.mark.parametrize("kind", ["normal", "none"])
+@pytest.mark.parametrize("D", [512, 64])
+def test_merge_of_more_segments_than_one_round(dev, oracle, D, kind):
+    """seg_len = 4 cuts the hub row into at least 175 segments.  The merge (agg_half_merge_kernel: unit_sum.hpp's
+    seg_merge at 8 channels a lane, written out) adds them in groups of 16, one group per team and round, T = 256 / LPE
+    teams: at D = 512 (LPE = 64, T = 4) a round takes 64 segments, so the hub needs three and ends on a partial group;
+    at D = 64 (LPE = 8, T = 32) it needs one, with most teams idle."""
+    g = GRAPHS["hub"](dev)
+    n, seg_len = g.number_of_nodes(), 4
+    T = 256 // max(8, min(64, D // 8))
+    plan = g.csr.plan(seg_len, need=True)
+    hub_segs = int(np.diff(plan["long_seg_ptr"].cpu().numpy()[:plan["n_long"] + 1]).max())
+    assert hub_segs >= 175 and hub_segs % 16 != 0, "the last group of the hub row is partial"
+    if D == 512:
+        assert T == 4 and plan["n_seg"] > 16 * T and hub_segs > 2 * 16 * T, "three rounds"
+    og = oracle_graph(oracle, g)
+    x = torch.randn(n, D, device=dev).to(torch.bfloat16)
+    ds = np.random.default_rng(D).uniform(0.5, 1.5, n).astype(np.float32)
+    dsd = torch.from_numpy(ds).to(dev)
+    p0, p1 = (None, None) if kind == "none" else _params(kind, 1, D, dev)
+    kw = dict(seed=13, offset=4)
+    noise = None if kind == "none" else _noise(g, D, kind, p0, p1, **kw)
+    spec = _ospec(oracle, g, D, kind, p0, p1, **kw)
+    for reduce in ("sum", "mean"):
+        with hw_normals(oracle, dev):
+            ref = oracle.agg_fwd(og, x.float().cpu().numpy(), spec, dst_scale=ds,
+                                 reduce=oracle.REDUCE_MEAN if reduce == "mean" else oracle.REDUCE_SUM)
+        got = _raw(g.csr, x, noise, reduce, None, dsd, seg_len=seg_len)
+        assert_close(got, ref, what=f"D={D} {kind} {reduce} seg_len={seg_len}")
+        again = _raw(g.csr, x, noise, reduce, None, dsd, seg_len=seg_len)
+        assert torch.equal(again.view(torch.int32), got.view(torch.int32)), "two launches, the same bits"
+        whole = _raw(g.csr, x, noise, reduce, None, dsd, seg_len=0)             # no plan: the hub row is one unit
+        assert_close(got, whole.cpu().numpy(), what=f"D={D} {kind} {reduce} seg_len={seg_len} against no plan")
+
+
 # ---- 5. strided input -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dname", list(DTYPES))
 def test_strided_rows_and_misaligned_rows(dev, oracle, dname, monkeypatch):

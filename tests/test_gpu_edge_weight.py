@@ -76,11 +76,11 @@ def _oref(O, og, x, w1, reduce="sum", ss=None, ds=None):
     return O.agg_fwd(og, x, spec, reduce=O.REDUCE_MEAN if reduce == "mean" else O.REDUCE_SUM, src_scale=ss, dst_scale=ds)
 
 
-def _raw(csrv, x, noise=None, w=None, reduce="sum", ss=None, ds=None):
+def _raw(csrv, x, noise=None, w=None, reduce="sum", ss=None, ds=None, seg_len=SEG):
     """The entry point itself."""
     from stag_amd import ops
     spec = ops._targs_or_c(ops._noise_spec(noise)) if noise is not None else ops._targs_or_c(ops._explicit_spec(w))
-    return ops._agg_w1_raw(csrv, x, x.shape[1], spec, ops._REDUCE[reduce], ss, ds, SEG)
+    return ops._agg_w1_raw(csrv, x, x.shape[1], spec, ops._REDUCE[reduce], ss, ds, seg_len)
 
 
 # ---- 1. values -----------------------------------------------------------------------------------------------------
@@ -299,6 +299,41 @@ def test_two_calls_give_the_same_bits_and_every_route_agrees(dev, graph_a, monke
     got = ops.aggregate(g, row, wt, _broadcast_x=True)
     ref = ops.aggregate(g, row.expand(n, 20).contiguous(), wt.expand(E, 20).contiguous())
     assert_close(got, ref.cpu().numpy(), what="broadcast row")
+
+
+@pytest.mark.parametrize("kind", ["normal", "explicit"])
+@pytest.mark.parametrize("D", [256, 16])
+def test_merge_of_more_segments_than_one_round(dev, oracle, graph_a, D, kind):
+    """seg_len = 4 cuts the hub row into at least 275 segments.  The merge (unit_sum.hpp's seg_merge at 4 channels a
+    lane) adds them in groups of 16, one group per team and round, T = 256 / LPE teams: at D = 256 (LPE = 64, T = 4)
+    a round takes 64 segments, so the hub needs five and ends on a partial group; at D = 16 (LPE = 4, T = 64) one."""
+    g, seg_len = graph_a, 4
+    n, E = g.number_of_nodes(), g.number_of_edges()
+    T = 256 // max(4, min(64, D // 4))
+    plan = g.csr.plan(seg_len, need=True)
+    hub_segs = int(np.diff(plan["long_seg_ptr"].cpu().numpy()[:plan["n_long"] + 1]).max())
+    assert hub_segs >= 275 and hub_segs % 16 != 0, "the last group of the hub row is partial"
+    if D == 256:
+        assert T == 4 and plan["n_seg"] > 16 * T and hub_segs > 4 * 16 * T, "five rounds"
+    og = oracle_graph(oracle, g)
+    x = torch.randn(n, D, device=dev)
+    ds = np.random.default_rng(D).uniform(0.5, 1.5, n).astype(np.float32)
+    dsd = torch.from_numpy(ds).to(dev)
+    if kind == "explicit":
+        wt = torch.randn(E, 1, device=dev)
+        how, w1 = dict(w=wt), wt.cpu().numpy()
+    else:
+        v = _kinds(E, dev)[kind]
+        how = dict(noise=_noise(g, *v, seed=8, offset=5))
+        with hw_normals(oracle, dev):
+            w1 = _ow1(oracle, og, E, *v, seed=8, offset=5)
+    for reduce in ("sum", "mean"):
+        got = _raw(g.csr, x, reduce=reduce, ds=dsd, seg_len=seg_len, **how)
+        assert_close(got, _oref(oracle, og, x.cpu().numpy(), w1, reduce, None, ds), what=f"D={D} {kind} {reduce} seg_len=4")
+        again = _raw(g.csr, x, reduce=reduce, ds=dsd, seg_len=seg_len, **how)
+        assert torch.equal(again.view(torch.int32), got.view(torch.int32)), "two launches, the same bits"
+        whole = _raw(g.csr, x, reduce=reduce, ds=dsd, seg_len=0, **how)             # no plan: the hub row is one unit
+        assert_close(got, whole.cpu().numpy(), what=f"D={D} {kind} {reduce} seg_len=4 against no plan")
 
 
 def test_other_widths_keep_their_error(dev, graph_c):
