@@ -107,8 +107,10 @@ class StagLayer(torch.nn.Module):
         """True if a forward pass takes exactly one offset from the generator (a fusable q_a)."""
         try:
             return fusable(self.q_a.base_distribution)
-        except Exception:      # an AmortizedDistribution that was never conditioned
-            return False
+        except Exception:      # an AmortizedDistribution that was never conditioned: its class says what it will draw
+            from .noise import _KIND_OF
+            return (getattr(self.q_a, "new_parameters", 0) is None
+                    and getattr(self.q_a, "base_distribution_class", None) in _KIND_OF)
 
     def offsets_per_forward(self):
         """Offsets of the generator one forward pass consumes: one per fused draw, plus what the base layer draws
@@ -153,7 +155,12 @@ class StagLayer(torch.nn.Module):
         w = self._descriptor(graph, dn, dist, relu=self.relu, in_norm=self.norm, differentiable=live, seed=gen.seed,
                              offset=gen.offset, epoch=gen.device_epoch)
         if w.param_mode > _lib.PARAM_PER_CHANNEL:
-            return None
+            # amortised [E, 1] parameters batch on a base layer whose noise width is the feature width
+            # (stag_agg_fwd_mc_edge); GAT (width = heads) and [E, Dn] parameters keep the loop
+            from . import ops as _ops
+            if (w.param_mode != _lib.PARAM_PER_EDGE1 or isinstance(self.base_layer, GAT)
+                    or _ops.mc_edge_why_not(feat, w, graph) is not None):
+                return None
         gen.next_offset()
         w.n_samples, w.offset_stride = int(n_samples), int(offset_stride)
         self._edge_weight_handle = None      # no single [E, Dn] sample stands for this call: mc_select(s) names one

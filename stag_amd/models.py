@@ -75,7 +75,8 @@ class StagModel(torch.nn.Module):
         base + s * L and its other layers from base + s * L + 1 on.  Under autograd, with the first layer's input
         data and its noise fixed (every `*_mle` script), the batched aggregation needs no backward at all — the dense
         transform differentiates through the S outputs; with a learned (`vi=True`) first layer or an input that carries
-        a gradient the forward is still batched and the backward is the loop's per-sample passes (ops._AggregateMC)."""
+        a gradient the forward is still batched and the backward is the loop's per-sample passes (ops._AggregateMC; for the
+        [E, 1] heads of an AmortizedDistribution(in, 1): stag_agg_fwd_mc_edge and ops._AggregateMCEdge)."""
         plan = self._mc_plan(graph, feat, n_samples)
         if plan is None:
             for _ in range(n_samples):
