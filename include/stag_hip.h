@@ -273,6 +273,38 @@ int stag_plan_xcd_device_count(const stag_unit* units, int32_t n_units, int32_t 
 int stag_plan_xcd_device_fill(const stag_unit* units, int32_t n_units, const int32_t* strides, int32_t fine, int32_t* xcd,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the share order of a plan's units (additive in v19) ----
+ * A second array of the SAME unit records, in which whole-row units that gather the same source row lie side by side:
+ * the teams of one workgroup then ask for that row within the same few microseconds, and all but the first request can
+ * be served by the L2 instead of crossing the fabric again.  For graphs whose sources are NOT near their destinations
+ * (where xcd_order has nothing to offer).  Hand it to an aggregation entry point as plan.units, the other fields as they
+ * are: every result is bit-identical to plan order (no arithmetic depends on the order of whole-row units).
+ *   - records [0, n_seg) — the segments, slot == index — stay where they are;
+ *   - the rest is a permutation of the whole-row records that moves a record only inside its class of equal trip count
+ *     (len + 1) / 2: length order between classes, "long first" and the n_heavy prefix (16 | 17 edges is a class
+ *     boundary) survive;
+ *   - groups are aligned to ABSOLUTE unit indices: a pair that shares a source lies at 2k, 2k + 1, a quad (two such pairs
+ *     that share one) at 4k ... 4k + 3, an octet at 8k ... 8k + 7, so a workgroup of 4, 8 or 16 units sees whole groups;
+ *     the hole in front of a class's first multiple of 8 is filled with its ungrouped units (with too few of those, the
+ *     last group of the next size is taken apart; a class that ends inside the block of 8 it starts in keeps pairs only);
+ *   - the same graph gives the same ints on every build (integer atomicMin of (hash, partner); nothing depends on
+ *     scheduling).  The two builders follow different merge rules and need not agree with each other:
+ *       stag_plan_share         host records and indices; the sequential greedy: clusters in index order, each merged
+ *                               with the first free cluster of its class that shares one of its sources; 1 -> 2 -> 4 -> 8;
+ *       stag_plan_share_device  device records and indices; per level a rocPRIM sort of the (source, cluster) pairs, every
+ *                               cluster choosing among its neighbours in a run of one source, mutual choices merged, four
+ *                               rounds.  No read-back, no synchronisation; not inside a hipGraph capture (it is built
+ *                               once per view).  workspace >= stag_plan_share_device_workspace_bytes(...), 16-byte aligned.
+ * seg_len: the plan's (no whole-row unit is longer).  units_out != units, 16-byte aligned on the device.
+ * STAG_EINVAL: counts out of order (0 <= n_seg <= n_heavy <= n_units), seg_len outside [1, 2^20], a NULL array that is
+ * needed; STAG_ENOMEM: workspace NULL or too small (host: allocation failed).                                          */
+int stag_plan_share(const stag_unit* units_host, int32_t n_units, int32_t n_seg, int32_t n_heavy, int32_t seg_len,
+                    const int32_t* indices_host, int64_t n_edges, stag_unit* units_out_host);
+size_t stag_plan_share_device_workspace_bytes(int32_t n_units, int64_t n_edges, int32_t seg_len);
+int stag_plan_share_device(const stag_unit* units, int32_t n_units, int32_t n_seg, int32_t n_heavy, int32_t seg_len,
+                           const int32_t* indices, int64_t n_edges, stag_unit* units_out, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* int32 arrays laid end to end with offsets, every piece of every array in ONE launch: what a block-diagonal batch
  * (`dgl.batch`, scripts/ppi_mle/run.py:12-14) needs to take its CSR views from its parts' — row pointers shifted by the
  * edges before the part, column ids by its nodes, edge ids and forward positions by its edges (stag_amd/graph.py: batch).

@@ -123,6 +123,11 @@ def bind(path):
     l.stag_plan_xcd_device_workspace_bytes.argtypes = [C.c_int32]
     l.stag_plan_xcd_device_count.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _vp, _vp, C.c_size_t, _vp]
     l.stag_plan_xcd_device_fill.argtypes = [_vp, C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp]
+    l.stag_plan_share.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int64, _vp]
+    l.stag_plan_share_device_workspace_bytes.restype = C.c_size_t
+    l.stag_plan_share_device_workspace_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]
+    l.stag_plan_share_device.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp,
+                                         C.c_size_t, _vp]
     l.stag_plan_device_workspace_bytes.restype = C.c_size_t
     l.stag_plan_device_workspace_bytes.argtypes = [C.c_int32]
     l.stag_plan_device.argtypes = [_vp, C.c_int32, C.c_int64, C.c_int32, _vp, C.c_int64, _vp, _vp, C.c_int64,

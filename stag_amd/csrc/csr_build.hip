@@ -8,10 +8,13 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <utility>
+#include <vector>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include "../../include/stag_hip.h"
+#include "share_order.hpp"
 
 namespace {
 
@@ -449,4 +452,310 @@ extern "C" int stag_concat_jobs(const stag_concat_job* jobs, const int64_t* chun
   if (!jobs || !chunk_start) return STAG_EINVAL;
   hipLaunchKernelGGL(concat_jobs_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, jobs, chunk_start, n_jobs);
   return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
+}
+
+// ---- the share order of a plan's units (stag_plan_share / stag_plan_share_device) ---------------------------------
+// Whole-row units that gather the same source row are put side by side — pairs at 2k, quads at 4k, octets at 8k of the
+// absolute unit index — inside their class of equal trip count (len + 1) / 2, so that the teams of one workgroup ask
+// for a shared row within the same few microseconds and the second request finds it in the L2.  Segments stay put.
+//   per level (1 -> 2 -> 4 -> 8): the (source, cluster) pair of every edge of every cluster that is complete at this
+//   size, sorted; a cluster's id is its smallest unit index, so inside a run of one source the clusters of one class are
+//   neighbours.  Device: every cluster takes, of its neighbours in such runs, the one with the smallest hash (atomicMin
+//   of (hash, partner): a pure function of the graph); mutual choices merge; kShareRounds rounds.  Host: the sequential
+//   greedy — clusters in id order, each takes the first free cluster that shares one of its sources.
+//   Then one sort of the unit keys (share_order.hpp) ranks every class, and share_layout / share_position place it.
+namespace {
+
+constexpr int kShareRounds = 4;
+constexpr int kShareScan = 16;      // entries of a run a cluster looks ahead for a free neighbour
+
+__global__ void share_init_kernel(int32_t n_seg, int32_t n_units, int32_t* cid, int32_t* lvl, int32_t* off) {
+  const int32_t i = n_seg + blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_units) return;
+  cid[i] = i; lvl[i] = 0; off[i] = 0;
+}
+
+// keys[p] = (source, cluster) for the edges of the clusters complete at `level`; every other position keeps ~0
+__global__ void share_edge_keys_kernel(const stag_unit* units, int32_t n_seg, int32_t n_units, const int32_t* indices,
+                                       int64_t E, const int32_t* cid, const int32_t* lvl, int32_t level, uint64_t* keys) {
+  const int32_t i = n_seg + blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_units || lvl[i] != level) return;
+  const stag_unit u = units[i];
+  const uint64_t c = (uint32_t)cid[i];
+  for (int32_t e = 0; e < u.len; ++e) {
+    const int64_t p = (int64_t)u.start + e;
+    if (p < 0 || p >= E) break;
+    keys[p] = ((uint64_t)(uint32_t)indices[p] << 32) | c;
+  }
+}
+
+__global__ void share_candidates_kernel(const stag_unit* units, const uint64_t* keys_s, int64_t E, const int32_t* mate,
+                                        uint32_t salt, unsigned long long* best) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= E) return;
+  const uint64_t k = keys_s[j];
+  if (k == ~0ull) return;
+  const uint32_t A = (uint32_t)k, src = (uint32_t)(k >> 32);
+  if (mate[A] >= 0) return;
+  const int32_t trips = share_trips(units[A].len);
+  for (int64_t t = j + 1; t < E && t <= j + kShareScan; ++t) {
+    const uint64_t kt = keys_s[t];
+    if (kt == ~0ull || (uint32_t)(kt >> 32) != src) return;
+    const uint32_t B = (uint32_t)kt;
+    if (B == A) continue;
+    if (share_trips(units[B].len) != trips) return;       // ids ascend with the class: the run's later clusters differ too
+    if (mate[B] >= 0) continue;
+    const unsigned long long h = (unsigned long long)share_hash(A, B, salt) << 32;
+    atomicMin(best + A, h | B);
+    atomicMin(best + B, h | A);
+    return;
+  }
+}
+
+__global__ void share_mutual_kernel(int32_t n_seg, int32_t n_units, const int32_t* cid, const int32_t* lvl, int32_t level,
+                                    const unsigned long long* best, int32_t* mate) {
+  const int32_t A = n_seg + blockIdx.x * blockDim.x + threadIdx.x;
+  if (A >= n_units || lvl[A] != level || cid[A] != A) return;
+  const unsigned long long b = best[A];
+  if (b == ~0ull) return;
+  const int32_t B = (int32_t)(uint32_t)b;
+  // (only the smaller id of a mutual pair writes, and a cluster's choice names one partner: no two threads write one slot)
+  if (A < B && B < n_units && (uint32_t)best[B] == (uint32_t)A) { mate[A] = B; mate[B] = A; }
+}
+
+__global__ void share_merge_kernel(int32_t n_seg, int32_t n_units, const int32_t* mate, int32_t level, int32_t* cid,
+                                   int32_t* lvl, int32_t* off) {
+  const int32_t i = n_seg + blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_units || lvl[i] != level) return;
+  const int32_t c = cid[i], m = mate[c];
+  if (m < 0) return;
+  if (m < c) { cid[i] = m; off[i] += 1 << level; }
+  lvl[i] = level + 1;
+}
+
+__global__ void share_unit_keys_kernel(const stag_unit* units, int32_t n_seg, int32_t n_units, int32_t seg_len,
+                                       const int32_t* cid, const int32_t* lvl, const int32_t* off, uint64_t* keys, int32_t* idx) {
+  const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  const int32_t i = n_seg + j;
+  if (i >= n_units) return;
+  keys[j] = share_unit_key(share_class(units[i].len, seg_len), lvl[i], cid[i], off[i]);
+  idx[j] = i;
+}
+
+// table[c] = the layout of class index c, from the sorted unit keys (5 lower bounds)
+__global__ void share_table_kernel(const uint64_t* keys_s, int32_t n_w, int32_t n_seg, int32_t n_classes, ShareLayout* table) {
+  const int32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_classes) return;
+  int32_t at[5];
+  for (int q = 0; q < 5; ++q) {
+    const uint64_t want = ((uint64_t)(uint32_t)c << kShareClassShift) + ((uint64_t)q << kShareSizeShift);
+    int32_t lo = 0, hi = n_w;
+    while (lo < hi) {
+      const int32_t mid = lo + (hi - lo) / 2;
+      if (keys_s[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    at[q] = lo;
+  }
+  table[c] = share_layout(n_seg + at[0], n_seg + at[4], (at[1] - at[0]) / 8, (at[2] - at[1]) / 4, (at[3] - at[2]) / 2,
+                          at[4] - at[3]);
+}
+
+__global__ void share_place_kernel(const stag_unit* units, const uint64_t* keys_s, const int32_t* idx_s, int32_t n_seg,
+                                   int32_t n_units, const ShareLayout* table, stag_unit* out) {
+  const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_units) return;
+  if (j < n_seg) { reinterpret_cast<int4*>(out)[j] = reinterpret_cast<const int4*>(units)[j]; return; }
+  const int32_t s = j - n_seg;
+  const ShareLayout L = table[(int32_t)(keys_s[s] >> kShareClassShift)];
+  int32_t pos = share_position(L, j - L.a);
+  if (pos < n_seg || pos >= n_units) pos = j;             // (cannot happen: share_layout fills [a, b) exactly)
+  reinterpret_cast<int4*>(out)[pos] = reinterpret_cast<const int4*>(units)[idx_s[s]];
+}
+
+struct ShareWs {
+  uint64_t *keys, *keys_s;
+  unsigned long long* best;
+  int32_t *cid, *lvl, *off, *mate, *idx, *idx_s;
+  ShareLayout* table;
+  void* tmp;
+  size_t tmp_bytes, total;
+};
+
+int32_t share_classes(int32_t seg_len) { return share_trips(seg_len) + 1; }
+
+ShareWs share_ws(void* workspace, int32_t n_units, int64_t n_edges, int32_t seg_len) {
+  char* w = static_cast<char*>(workspace);
+  const size_t nu = (size_t)(n_units > 0 ? n_units : 1);
+  const size_t m = std::max(nu, (size_t)(n_edges > 0 ? n_edges : 1));
+  size_t sort_keys = 0, sort_pairs = 0;
+  uint64_t* k64 = nullptr;
+  int32_t* null = nullptr;
+  (void)rocprim::radix_sort_keys(nullptr, sort_keys, k64, k64, m, 0u, 64u);
+  (void)rocprim::radix_sort_pairs(nullptr, sort_pairs, k64, k64, null, null, nu, 0u, (unsigned)kShareKeyBits);
+  ShareWs x;
+  size_t at = 0;
+  auto take = [&](size_t bytes) { char* p = w ? w + at : nullptr; at += align_up(bytes); return p; };
+  x.keys = reinterpret_cast<uint64_t*>(take(m * 8));
+  x.keys_s = reinterpret_cast<uint64_t*>(take(m * 8));
+  x.best = reinterpret_cast<unsigned long long*>(take(nu * 8));
+  x.cid = reinterpret_cast<int32_t*>(take(nu * 4));
+  x.lvl = reinterpret_cast<int32_t*>(take(nu * 4));
+  x.off = reinterpret_cast<int32_t*>(take(nu * 4));
+  x.mate = reinterpret_cast<int32_t*>(take(nu * 4));
+  x.idx = reinterpret_cast<int32_t*>(take(nu * 4));
+  x.idx_s = reinterpret_cast<int32_t*>(take(nu * 4));
+  x.table = reinterpret_cast<ShareLayout*>(take((size_t)share_classes(seg_len) * sizeof(ShareLayout)));
+  x.tmp_bytes = align_up(std::max(sort_keys, sort_pairs));
+  x.tmp = take(x.tmp_bytes);
+  x.total = at;
+  return x;
+}
+
+bool share_args_ok(const void* units, int32_t n_units, int32_t n_seg, int32_t n_heavy, int32_t seg_len, const void* indices,
+                   int64_t n_edges, const void* out) {
+  return n_units >= 0 && n_seg >= 0 && n_seg <= n_heavy && n_heavy <= n_units && seg_len > 0 && seg_len <= (1 << 20) &&
+         n_edges >= 0 && (n_units == 0 || (units && out && units != out)) && (n_edges == 0 || indices);
+}
+
+}  // namespace
+
+extern "C" size_t stag_plan_share_device_workspace_bytes(int32_t n_units, int64_t n_edges, int32_t seg_len) {
+  if (seg_len <= 0 || seg_len > (1 << 20)) seg_len = 1;
+  return share_ws(nullptr, n_units, n_edges, seg_len).total;
+}
+
+extern "C" int stag_plan_share_device(const stag_unit* units, int32_t n_units, int32_t n_seg, int32_t n_heavy, int32_t seg_len,
+                                      const int32_t* indices, int64_t n_edges, stag_unit* units_out, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  if (!share_args_ok(units, n_units, n_seg, n_heavy, seg_len, indices, n_edges, units_out) || ((uintptr_t)units & 15) ||
+      ((uintptr_t)units_out & 15)) return STAG_EINVAL;
+  if (n_units == 0) return STAG_OK;
+  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < stag_plan_share_device_workspace_bytes(n_units, n_edges, seg_len))
+    return STAG_ENOMEM;
+  hipStream_t s = (hipStream_t)stream;
+  const ShareWs x = share_ws(workspace, n_units, n_edges, seg_len);
+  const int32_t n_w = n_units - n_seg;
+  const dim3 block(256), grid_u((unsigned)((n_units + 255) / 256)), grid_w((unsigned)((n_w + 255) / 256));
+  if (n_w > 0 && n_edges > 0) {
+    const dim3 grid_e((unsigned)((n_edges + 255) / 256));
+    hipLaunchKernelGGL(share_init_kernel, grid_w, block, 0, s, n_seg, n_units, x.cid, x.lvl, x.off);
+    for (int level = 0; level < kShareLevels; ++level) {
+      if (hipMemsetAsync(x.keys, 0xFF, (size_t)n_edges * 8, s) != hipSuccess) return STAG_EIO;
+      if (hipMemsetAsync(x.mate, 0xFF, (size_t)n_units * 4, s) != hipSuccess) return STAG_EIO;
+      hipLaunchKernelGGL(share_edge_keys_kernel, grid_w, block, 0, s, units, n_seg, n_units, indices, n_edges, x.cid, x.lvl,
+                         level, x.keys);
+      size_t tmp_bytes = x.tmp_bytes;
+      if (rocprim::radix_sort_keys(x.tmp, tmp_bytes, x.keys, x.keys_s, (size_t)n_edges, 0u, 64u, s) != hipSuccess) return STAG_EIO;
+      for (int round = 0; round < kShareRounds; ++round) {
+        if (hipMemsetAsync(x.best, 0xFF, (size_t)n_units * 8, s) != hipSuccess) return STAG_EIO;
+        hipLaunchKernelGGL(share_candidates_kernel, grid_e, block, 0, s, units, x.keys_s, n_edges, x.mate,
+                           (uint32_t)(level * kShareRounds + round), x.best);
+        hipLaunchKernelGGL(share_mutual_kernel, grid_w, block, 0, s, n_seg, n_units, x.cid, x.lvl, level, x.best, x.mate);
+      }
+      hipLaunchKernelGGL(share_merge_kernel, grid_w, block, 0, s, n_seg, n_units, x.mate, level, x.cid, x.lvl, x.off);
+    }
+  } else if (n_w > 0) {
+    hipLaunchKernelGGL(share_init_kernel, grid_w, block, 0, s, n_seg, n_units, x.cid, x.lvl, x.off);
+  }
+  if (n_w > 0) {
+    hipLaunchKernelGGL(share_unit_keys_kernel, grid_w, block, 0, s, units, n_seg, n_units, seg_len, x.cid, x.lvl, x.off,
+                       x.keys, x.idx);
+    size_t tmp_bytes = x.tmp_bytes;
+    if (rocprim::radix_sort_pairs(x.tmp, tmp_bytes, x.keys, x.keys_s, x.idx, x.idx_s, (size_t)n_w, 0u, (unsigned)kShareKeyBits,
+                                  s) != hipSuccess) return STAG_EIO;
+    const int32_t n_classes = share_classes(seg_len);
+    hipLaunchKernelGGL(share_table_kernel, dim3((unsigned)((n_classes + 255) / 256)), block, 0, s, x.keys_s, n_w, n_seg,
+                       n_classes, x.table);
+  }
+  hipLaunchKernelGGL(share_place_kernel, grid_u, block, 0, s, units, x.keys_s, x.idx_s, n_seg, n_units, x.table, units_out);
+  return hipGetLastError() == hipSuccess ? STAG_OK : STAG_EIO;
+}
+
+// The host twin: the sequential greedy, the same layout.
+extern "C" int stag_plan_share(const stag_unit* units_host, int32_t n_units, int32_t n_seg, int32_t n_heavy, int32_t seg_len,
+                               const int32_t* indices_host, int64_t n_edges, stag_unit* units_out_host) {
+  if (!share_args_ok(units_host, n_units, n_seg, n_heavy, seg_len, indices_host, n_edges, units_out_host)) return STAG_EINVAL;
+  try {
+    const stag_unit* U = units_host;
+    std::vector<int32_t> cid(n_units), lvl(n_units, 0), off(n_units, 0), next(n_units, -1), mate(n_units);
+    for (int32_t i = 0; i < n_units; ++i) cid[i] = i;
+    struct Entry { int32_t trips_desc, src, c; };
+    std::vector<Entry> run;
+    std::vector<size_t> cursor;
+    for (int level = 0; level < kShareLevels; ++level) {
+      // (class, source, cluster) of every edge of the clusters complete at this size; next[] chains a cluster's units
+      run.clear();
+      for (int32_t i = n_seg; i < n_units; ++i) {
+        if (lvl[i] != level) continue;
+        for (int32_t e = 0; e < U[i].len; ++e) {
+          const int64_t p = (int64_t)U[i].start + e;
+          if (p < 0 || p >= n_edges) break;
+          run.push_back(Entry{-share_trips(U[i].len), indices_host[p], cid[i]});
+        }
+      }
+      auto less = [](const Entry& x, const Entry& y) {
+        return x.trips_desc != y.trips_desc ? x.trips_desc < y.trips_desc : x.src != y.src ? x.src < y.src : x.c < y.c;
+      };
+      std::sort(run.begin(), run.end(), less);
+      cursor.assign(run.size(), 0);
+      for (size_t k = 0; k < run.size(); ++k) cursor[k] = k;
+      std::fill(mate.begin(), mate.end(), -1);
+      for (int32_t A = n_seg; A < n_units; ++A) {
+        if (lvl[A] != level || cid[A] != A || mate[A] >= 0) continue;
+        int32_t found = -1;
+        for (int32_t m = A; m >= 0 && found < 0; m = next[m]) {               // the cluster's units, in member order
+          for (int32_t e = 0; e < U[m].len && found < 0; ++e) {
+            const int64_t p = (int64_t)U[m].start + e;
+            if (p < 0 || p >= n_edges) break;
+            const Entry want{-share_trips(U[A].len), indices_host[p], 0};
+            const size_t first = std::lower_bound(run.begin(), run.end(), want, less) - run.begin();
+            if (first >= run.size()) continue;
+            auto in_run = [&](size_t k) {
+              return k < run.size() && run[k].trips_desc == want.trips_desc && run[k].src == want.src;
+            };
+            size_t k = cursor[first];                     // (the taken clusters at the run's head are passed over once)
+            while (in_run(k) && mate[run[k].c] >= 0) ++k;
+            cursor[first] = k;
+            for (; in_run(k); ++k)
+              if (run[k].c != A && mate[run[k].c] < 0) { found = run[k].c; break; }
+          }
+        }
+        if (found >= 0) { mate[A] = found; mate[found] = A; }
+      }
+      for (int32_t A = n_seg; A < n_units; ++A) {       // A < mate[A]: the clusters were visited in id order
+        if (lvl[A] != level || cid[A] != A || mate[A] < A) continue;
+        int32_t tail = A;
+        while (next[tail] >= 0) tail = next[tail];
+        next[tail] = mate[A];
+      }
+      for (int32_t i = n_seg; i < n_units; ++i) {
+        if (lvl[i] != level) continue;
+        const int32_t c = cid[i], m = mate[c];
+        if (m < 0) continue;
+        if (m < c) { cid[i] = m; off[i] += 1 << level; }
+        lvl[i] = level + 1;
+      }
+    }
+    const int32_t n_w = n_units - n_seg;
+    std::vector<std::pair<uint64_t, int32_t>> keyed(n_w);
+    for (int32_t j = 0; j < n_w; ++j) {
+      const int32_t i = n_seg + j;
+      keyed[j] = {share_unit_key(share_class(U[i].len, seg_len), lvl[i], cid[i], off[i]), i};
+    }
+    std::sort(keyed.begin(), keyed.end());
+    std::copy(U, U + n_seg, units_out_host);
+    for (int32_t j = 0; j < n_w;) {
+      const uint64_t cls = keyed[j].first >> kShareClassShift;
+      int32_t at[5] = {j, j, j, j, j}, e = j;
+      for (; e < n_w && (keyed[e].first >> kShareClassShift) == cls; ++e)
+        for (int q = (int)((keyed[e].first >> kShareSizeShift) & 3) + 1; q < 5; ++q) at[q] = e + 1;
+      const ShareLayout L = share_layout(n_seg + j, n_seg + e, (at[1] - at[0]) / 8, (at[2] - at[1]) / 4, (at[3] - at[2]) / 2,
+                                         at[4] - at[3]);
+      for (int32_t r = j; r < e; ++r) units_out_host[share_position(L, r - j)] = U[keyed[r].second];
+      j = e;
+    }
+  } catch (...) {
+    return STAG_ENOMEM;
+  }
+  return STAG_OK;
 }

@@ -53,6 +53,13 @@ MERGE_HEAVY_WIDE = os.environ.get("STAG_XCD_MERGE_HEAVY", "1") != "0"
 GRAPHS_ABOVE = int(os.environ.get("STAG_XCD_GRAPHS_ABOVE", "128"))         # floats per row
 MERGE_HEAVY_ABOVE = int(os.environ.get("STAG_XCD_MERGE_ABOVE", "128"))     # floats per row
 PLAN_AFTER_LAUNCHES = 16     # launches a short-row view runs without a plan before one is built for it
+# The share order (stag_plan_share_device: whole-row units that gather the same source row side by side, bit-identical
+# results) is for the views the XCD-aware order has nothing to offer: "auto" = a view that was declined the XCD order by
+# its stripe locality gets it once it has been launched SHARE_AFTER_LAUNCHES times; "1" with the plan; "0" never.  A plan
+# whose unit order the caller settled (plan["xcd_decided"] set from outside) and a plan with the XCD order keep theirs.
+SHARE_ORDER = os.environ.get("STAG_SHARE_ORDER", "auto")
+SHARE_MIN_WIDTH = 64         # floats per row: 16 lanes a row and up (narrower, a drawing launch lost 1 %: profiles/r18)
+SHARE_AFTER_LAUNCHES = 836   # (build time on the arxiv view) / (saving per launch), rounded up: DESIGN.md section 4.1
 
 
 def xcd_graph_ranges(edge_cuts, rows, width, range_bytes=None, stripes=None, fine_max=None):
@@ -336,9 +343,57 @@ class CsrView:
             if self.indptr.is_cuda and torch.cuda.is_current_stream_capturing():
                 return                           # (read-backs: not inside a hipGraph capture; the next eager launch decides)
             if self.stripe_locality() < XCD_MIN_LOCALITY:
-                plan["xcd_decided"] = True
+                plan["xcd_decided"] = plan["xcd_declined"] = True
                 return
         self._add_xcd_order(plan)
+
+    def share_units(self, plan, width=None):
+        """The share-ordered unit records of `plan` (same records, same counts) for a launch on rows of `width` floats,
+        or None: it has none (see SHARE_ORDER), the XCD-aware order is in force, or the rows are narrower than
+        SHARE_MIN_WIDTH and the order was not forced (STAG_SHARE_ORDER=1)."""
+        if plan.get("xcd_on") or (width is not None and width < SHARE_MIN_WIDTH and not plan.get("share_forced")):
+            return None
+        return plan.get("share")
+
+    def _build_share_units(self, plan):
+        """stag_plan_share_device on device records, stag_plan_share (the sequential greedy) on host records."""
+        lib, units, nu = _lib.lib(), plan["units"], plan["n_units"]
+        counts = (nu, plan["n_seg"], plan["n_heavy"], plan["seg_len"])
+        if units.is_cuda:
+            dev = units.device
+            out = torch.empty((max(nu, 1), 4), dtype=torch.int32, device=dev)
+            nbytes = lib.stag_plan_share_device_workspace_bytes(nu, self.n_edges, plan["seg_len"])
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            with _lib.on_device(dev):
+                _lib.check(lib.stag_plan_share_device(_lib.ptr(units), *counts, _lib.ptr(self.indices), self.n_edges,
+                                                      _lib.ptr(out), _lib.ptr(ws), nbytes, _lib.stream_of(dev)),
+                           "stag_plan_share_device")
+            return out
+        units_h = np.ascontiguousarray(units[:max(nu, 1)].numpy(), dtype=np.int32)
+        indices_h = np.ascontiguousarray(self.indices.numpy(), dtype=np.int32)
+        out_h = np.zeros_like(units_h)
+        _lib.check(lib.stag_plan_share(units_h.ctypes.data, *counts, indices_h.ctypes.data, self.n_edges, out_h.ctypes.data),
+                   "stag_plan_share")
+        return torch.from_numpy(out_h)
+
+    def _share_policy(self, plan):
+        """Called on every request for `plan`, behind _xcd_policy: see SHARE_ORDER."""
+        if plan.get("share_decided") or SHARE_ORDER == "0":
+            return
+        if plan.get("xcd_on") or (plan.get("xcd_decided") and not plan.get("xcd_declined")) or (
+                SHARE_ORDER == "auto" and self.n_src != self.n_dst):
+            plan["share_decided"] = True         # the XCD-aware order, an order the caller settled, a node-range shard's view
+            return
+        if SHARE_ORDER == "auto":
+            plan["share_uses"] = plan.get("share_uses", 0) + 1
+            if not plan.get("xcd_declined") or plan["share_uses"] <= SHARE_AFTER_LAUNCHES:
+                return
+        if self.indices.is_cuda and torch.cuda.is_current_stream_capturing():
+            return                               # (not inside a hipGraph capture; the next eager launch builds it)
+        plan["share_decided"] = True
+        if plan["n_units"] - plan["n_seg"] < 2 or self.n_edges == 0 or self.indices.dtype != torch.int32:
+            return
+        plan["share"], plan["share_forced"] = self._build_share_units(plan), SHARE_ORDER == "1"
 
     def _short_rows(self):
         """Every row has at most HEAVY_LEN edges (one device reduction and a one-number read-back, kept)."""
@@ -395,6 +450,7 @@ class CsrView:
                 counters={}, xcd=None, xcd_strides=(0, 0), **_block_plan(units, nu, dev))
         plan = self._plans[seg_len]
         self._xcd_policy(plan)
+        self._share_policy(plan)
         if need and plan.get("block_ptr") is None:
             # the unit batches of the cooperative GAT kernels: a greedy pass over the unit records on the host
             units_h = plan["units"][:max(plan["n_units"], 1)].cpu().numpy()
@@ -444,6 +500,20 @@ class CsrView:
         if XCD_ORDER == "1":
             self._add_xcd_order(sub)
         return sub
+
+
+def repeated_sources(units_host, n_seg, indices_host, block=8):
+    """How many edges of the whole-row units [n_seg, n_units) gather a source row that an earlier edge of the same aligned
+    block of `block` units (absolute unit indices) gathers too: the row fetches a workgroup could share.  Host arrays;
+    what the share order (stag_plan_share*) is judged by."""
+    units_host = np.asarray(units_host).reshape(-1, 4)[n_seg:]
+    lens = units_host[:, 2].astype(np.int64)
+    if lens.sum() == 0:
+        return 0
+    blk = np.repeat((np.arange(len(units_host), dtype=np.int64) + n_seg) // block, lens)
+    first = np.repeat(units_host[:, 1].astype(np.int64) - (np.cumsum(lens) - lens), lens)
+    src = np.asarray(indices_host, dtype=np.int64)[first + np.arange(lens.sum(), dtype=np.int64)]
+    return int(len(src) - len(np.unique(blk * (int(src.max()) + 1) + src)))
 
 
 def _block_plan(units_host, n_units, dev):

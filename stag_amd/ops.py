@@ -93,11 +93,13 @@ def _plan_counters(plan_t, tiles, dev):
     return key, counters
 
 
-def _plan_struct(csrv, seg_len, tiles, nbytes, dev, plan_t=None, width=None, gat_width=None, drawn=False):
+def _plan_struct(csrv, seg_len, tiles, nbytes, dev, plan_t=None, width=None, gat_width=None, drawn=False, share=0):
     """ctypes stag_plan for csrv (None when planning is off), plus the tensors it points into.
     plan_t: a sub-plan of csrv (CsrView.subplan) instead of its whole plan.  width: the row width of an aggregation
     launch — it may walk the plan's XCD-aware order (stag_plan.xcd_order).  gat_width: H * F of a cooperative GAT
-    launch — its unit batches may be the XCD-aware ones (stag_plan_blocks_xcd).  The other entry points use neither."""
+    launch — its unit batches may be the XCD-aware ones (stag_plan_blocks_xcd).  share: the row width (in fp32 lanes' worth of channels) of a
+    launch that walks whole-row units in any order and adds nothing across them — it takes the plan's share order
+    (CsrView.share_units) in place of its unit records where the view has one for this width.  The other entry points use none of these."""
     if plan_t is None:
         plan_t = csrv.plan(seg_len)
     if plan_t is None:
@@ -105,12 +107,15 @@ def _plan_struct(csrv, seg_len, tiles, nbytes, dev, plan_t=None, width=None, gat
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
     key, counters = _plan_counters(plan_t, tiles, dev)
     order, strides, fine = csrv.xcd_order(plan_t, width, drawn) if width and plan_t.get("xcd_on") else (None, (0, 0), 0)
-    units, block_ptr, n_blocks = plan_t["units"], plan_t["block_ptr"], plan_t["n_blocks"]
+    units, block_ptr, n_blocks, n_heavy = plan_t["units"], plan_t["block_ptr"], plan_t["n_blocks"], plan_t["n_heavy"]
     if gat_width and plan_t.get("xcd_on"):
         blocks = csrv.gat_blocks(plan_t, gat_width)
         if blocks is not None:
-            units, block_ptr, n_blocks, fine = blocks[0], blocks[1], blocks[2], -blocks[3]
+            units, block_ptr, n_blocks, fine, n_heavy = blocks[0], blocks[1], blocks[2], -blocks[3], 0
             order = units       # (non-NULL xcd_order: "these batches are XCD-local" — the GAT forward keeps two rows in flight)
+    shared = csrv.share_units(plan_t, share) if share else None
+    if shared is not None:
+        units, fine = shared, "share"      # (the same records, the same counts: only the struct's units pointer differs)
     # the struct is kept per (tiles, stream, order): only the workspace changes from call to call (host time of a
     # call matters on launch-bound graphs).  Safe to reuse: the library reads it during the call only.
     plan_c = plan_t.setdefault("_structs", {}).get(key + (fine,))
@@ -118,25 +123,35 @@ def _plan_struct(csrv, seg_len, tiles, nbytes, dev, plan_t=None, width=None, gat
         plan_c = _lib.Plan(plan_t["seg_len"], plan_t["n_units"], plan_t["n_long"], plan_t["n_seg"],
                            _lib.ptr(units), _lib.ptr(plan_t["long_rows"]),
                            _lib.ptr(plan_t["long_seg_ptr"]), _lib.ptr(counters), None, 0,
-                           plan_t["n_heavy"] if units is plan_t["units"] else 0, n_blocks, _lib.ptr(block_ptr),
+                           n_heavy, n_blocks, _lib.ptr(block_ptr),
                            _lib.ptr(order), *strides)
         plan_t["_structs"][key + (fine,)] = plan_c
     plan_c.workspace, plan_c.workspace_bytes = _lib.ptr(ws), nbytes
     return plan_c, (ws, counters)
 
 
+def _share_width(spec, D):
+    """The `share` argument of _plan_struct / _plan_args for a launch of this spec (either form): D, or 0 for the launch of
+    a shard (a node-range shard draws from pos_base, a channel shard from chunk_base), which keeps plan order."""
+    shard = (spec[1][2] or spec[0][6]) if isinstance(spec, tuple) else (spec.pos_base or spec.chunk_base)
+    return 0 if shard else D
+
+
 _NONE_ARGS = ([_lib.NOISE_NONE, 0, 0, 0, 0, 0, 0, 0], [0, 0, 0], [0.0, 0.0], None, None, None)
 
 
-def _plan_args(csrv, plan_t, tiles, dev, width=None, drawn=False):
-    """(units, long_rows, long_seg_ptr, block_ptr, xcd, counters, plan_ints) of torch.ops.stag.*"""
+def _plan_args(csrv, plan_t, tiles, dev, width=None, drawn=False, share=0):
+    """(units, long_rows, long_seg_ptr, block_ptr, xcd, counters, plan_ints) of torch.ops.stag.*
+    (width, drawn, share: as for _plan_struct)"""
     if plan_t is None:
         return (None, None, None, None, None, None, [0, 0, 0, 0, 0, 0, 0, 0])
     _, counters = _plan_counters(plan_t, tiles, dev)
     order, strides, _ = csrv.xcd_order(plan_t, width, drawn) if width and plan_t.get("xcd_on") else (None, (0, 0), 0)
     ints = [plan_t["seg_len"], plan_t["n_units"], plan_t["n_long"], plan_t["n_seg"], plan_t["n_heavy"], plan_t["n_blocks"],
             *strides]
-    return (plan_t["units"], plan_t["long_rows"], plan_t["long_seg_ptr"], plan_t["block_ptr"], order, counters, ints)
+    shared = csrv.share_units(plan_t, share) if share else None
+    return (plan_t["units"] if shared is None else shared, plan_t["long_rows"], plan_t["long_seg_ptr"], plan_t["block_ptr"],
+            order, counters, ints)
 
 
 def _agg_fwd_torch(csrv, x, noise_args, reduce, src_scale, dst_scale, seg_len, want_norm_scale, broadcast_x):
@@ -145,7 +160,8 @@ def _agg_fwd_torch(csrv, x, noise_args, reduce, src_scale, dst_scale, seg_len, w
     D = x.numel() if broadcast_x else x.shape[1]
     plan_t = csrv.plan(seg_len)
     out, ns = torch.ops.stag.agg_fwd(*csrv.torch_args(), *_plan_args(csrv, plan_t, (D + 255) // 256, dev, width=D,
-                                                                     drawn=noise_args[0][0] >= _lib.NOISE_NORMAL), x,
+                                                                     drawn=noise_args[0][0] >= _lib.NOISE_NORMAL,
+                                                                     share=_share_width(noise_args, D)), x,
                                      broadcast_x, *noise_args, reduce, src_scale, dst_scale, want_norm_scale)
     return out, (ns if want_norm_scale else None)
 
@@ -171,7 +187,7 @@ def _agg_raw(csrv, x, D, spec, reduce, src_scale, dst_scale, seg_len, want_norm_
     nbytes = (_lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], D, int(spec.in_norm))
               if plan_t is not None else 0)
     plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t, width=D,
-                                 drawn=spec.kind >= _lib.NOISE_NORMAL)
+                                 drawn=spec.kind >= _lib.NOISE_NORMAL, share=_share_width(spec, D))
     # (spec is the ctypes form from here on)
     cs = csrv.struct()
     with _lib.on_device(dev):
@@ -188,7 +204,7 @@ _HALF_DTYPES = {torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 
 def _unit_sum_raw(entry, csrv, x, x_args, D, spec, reduce, src_scale, dst_scale, seg_len, plan_t):
     """One launch of a plan-order sum entry point (stag_agg_fwd_half | stag_agg_fwd_w1) on csrv: out [n_dst, D] fp32.
-    x_args(): what the entry point takes between x and D.  Bound through ctypes only; the plan is walked in plan order."""
+    x_args(): what the entry point takes between x and D.  Bound through ctypes only; the plan is walked in plan order, or in the view's share order."""
     spec = _targs_or_c(spec)
     dev = _lib.require_device(x, csrv.indptr, src_scale, dst_scale)
     out = torch.empty((csrv.n_dst, D), dtype=torch.float32, device=dev)
@@ -197,7 +213,8 @@ def _unit_sum_raw(entry, csrv, x, x_args, D, spec, reduce, src_scale, dst_scale,
     if plan_t is None:
         plan_t = csrv.plan(seg_len)
     nbytes = _lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], D, 0) if plan_t is not None else 0
-    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t, width=None)
+    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t, width=None,
+                                 share=max(D // 2, 1) if entry == "stag_agg_fwd_half" else D)      # (a lane owns 8 halves)
     cs = csrv.struct()
     with _lib.on_device(dev):
         rc = getattr(_lib.lib(), entry)(
@@ -238,7 +255,8 @@ def _agg_bwd_raw(csrv_t, g, D, spec, g_scale, row_scale, seg_len, want_dp):
         dev = _lib.require_device(g, csrv_t.indptr, g_scale, row_scale)
         plan_t = csrv_t.plan(seg_len)
         dx, t0, t1 = torch.ops.stag.agg_bwd(*csrv_t.torch_args(), *_plan_args(csrv_t, plan_t, (D + 255) // 256, dev, width=D,
-                                                                               drawn=spec[0][0] >= _lib.NOISE_NORMAL),
+                                                                               drawn=spec[0][0] >= _lib.NOISE_NORMAL,
+                                                                               share=_share_width(spec, D)),
                                             g, *spec, g_scale, row_scale, want_dp)
         return dx, (t0 if want_dp else None), (t1 if want_dp else None)
     dev = _lib.require_device(g, csrv_t.indptr, g_scale, row_scale)
@@ -249,7 +267,7 @@ def _agg_bwd_raw(csrv_t, g, D, spec, g_scale, row_scale, seg_len, want_dp):
     nbytes = (_lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], (3 if want_dp else 1) * D, 0)
               if plan_t is not None else 0)
     plan_c, _keep = _plan_struct(csrv_t, seg_len, (D + 255) // 256, nbytes, dev, plan_t=plan_t, width=D,
-                                 drawn=spec.kind >= _lib.NOISE_NORMAL)
+                                 drawn=spec.kind >= _lib.NOISE_NORMAL, share=_share_width(spec, D))
     cs = csrv_t.struct()
     with _lib.on_device(dev):
         rc = _lib.lib().stag_agg_bwd(
@@ -272,7 +290,7 @@ def _agg_bwd_edge_raw(csrv_t, g, x, D, spec, g_scale, row_scale, seg_len, want_d
     e1 = torch.empty_like(e0)
     plan_t = csrv_t.plan(seg_len)
     nbytes = _lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], D, 0) if plan_t is not None else 0
-    plan_c, _keep = _plan_struct(csrv_t, seg_len, 1, nbytes, dev, plan_t=plan_t, width=D, drawn=True)
+    plan_c, _keep = _plan_struct(csrv_t, seg_len, 1, nbytes, dev, plan_t=plan_t, width=D, drawn=True, share=D)
     cs = csrv_t.struct()
     with _lib.on_device(dev):
         rc = _lib.lib().stag_agg_bwd_edge(
@@ -1464,7 +1482,7 @@ def _max_fwd_raw(csrv, x, D, spec, seg_len, want_cnt, broadcast_x=False):
     plan_t = csrv.plan(seg_len)
     if isinstance(spec, tuple):
         out, cnt = torch.ops.stag.agg_max_fwd(*csrv.torch_args(), *_plan_args(csrv, plan_t, (D + 255) // 256, dev, width=D,
-                                                                               drawn=drawn),
+                                                                               drawn=drawn, share=D),
                                               x, broadcast_x, *spec, bool(want_cnt))
         return out, (cnt if want_cnt else None)
     out = torch.empty((csrv.n_dst, D), dtype=torch.float32, device=dev)
@@ -1472,7 +1490,7 @@ def _max_fwd_raw(csrv, x, D, spec, seg_len, want_cnt, broadcast_x=False):
     if csrv.n_dst == 0:
         return out, cnt
     nbytes = _lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], 2 * D, 0) if plan_t is not None else 0
-    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t, width=D, drawn=drawn)
+    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t, width=D, drawn=drawn, share=D)
     cs = csrv.struct()
     with _lib.on_device(dev):
         rc = _lib.lib().stag_agg_max_fwd(C.byref(cs), C.byref(plan_c) if plan_c is not None else None, _lib.ptr(x),
@@ -1704,12 +1722,12 @@ def _agg_fwd_mc_raw(csrv, x, noise, n_samples, offset_stride, reduce, src_scale,
     dev = _lib.require_device(x, csrv.indptr, src_scale, dst_scale)
     if _torch_ext.available():      # the dispatcher op (csrc/torch_ext.cpp): same library call, visible to a compiled graph
         plan_t = csrv.plan(seg_len)
-        return torch.ops.stag.agg_fwd_mc(*csrv.torch_args(), *_plan_args(csrv, plan_t, (D + 255) // 256, dev, width=D, drawn=True),
+        return torch.ops.stag.agg_fwd_mc(*csrv.torch_args(), *_plan_args(csrv, plan_t, (D + 255) // 256, dev, width=D, drawn=True, share=D),
                                          x, *noise.torch_args(), int(n_samples), int(offset_stride), reduce, src_scale, dst_scale)
     out = torch.empty((n_samples, csrv.n_dst, D), dtype=torch.float32, device=dev)
     plan_t = csrv.plan(seg_len)
     nbytes = _lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], 4 * D, 0) if plan_t is not None else 0
-    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t=plan_t, width=D)
+    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t=plan_t, width=D, share=D)
     cs, spec = csrv.struct(), noise.spec()
     with _lib.on_device(dev):
         rc = _lib.lib().stag_agg_fwd_mc(
@@ -1825,7 +1843,8 @@ def mc_edge_why_not(x, noise, graph):
 
 
 def _agg_fwd_mc_edge_raw(csrv, x, noise, n_samples, offset_stride, reduce, src_scale, dst_scale, seg_len):
-    """One stag_agg_fwd_mc_edge call: [n_samples, n_dst, D].  Bound through ctypes only; the plan is walked in plan order."""
+    """One stag_agg_fwd_mc_edge call: [n_samples, n_dst, D].  Bound through ctypes only; the plan is walked in plan order, or in
+    the view's share order."""
     D = x.shape[1]
     dev = _lib.require_device(x, csrv.indptr, src_scale, dst_scale)
     out = torch.empty((n_samples, csrv.n_dst, D), dtype=torch.float32, device=dev)
@@ -1833,7 +1852,7 @@ def _agg_fwd_mc_edge_raw(csrv, x, noise, n_samples, offset_stride, reduce, src_s
         return out
     plan_t = csrv.plan(seg_len)
     nbytes = _lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], 4 * D, 0) if plan_t is not None else 0
-    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t=plan_t, width=None)
+    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t=plan_t, width=None, share=D)
     cs, spec = csrv.struct(), noise.spec()
     with _lib.on_device(dev):
         rc = _lib.lib().stag_agg_fwd_mc_edge(
