@@ -585,6 +585,36 @@ int stag_agg_fwd_mc_edge(const stag_csr* csr, const stag_plan* plan, const float
                          const float* src_scale, const float* dst_scale, float* out, int64_t ldo,
                          int64_t sample_stride, void* stream);
 
+/* ---- Monte-Carlo samples of amortised [E, D] edge noise from one pass over the rows and the parameter tables (both
+ * layers of `citation_rec/gcn`: an AmortizedDistribution(in, in) evaluated through model.forward / model.loss with
+ * n_samples > 1), additive in v19 ----
+ * n_samples draws of stag_agg_fwd with param_mode == STAG_PARAM_PER_EDGE from ONE pass over the gathered rows (up to 4
+ * samples per pass; more run in passes of 4, then 2, then 1, each starting at its own offset): sample s is stag_agg_fwd
+ * with spec.offset + s * offset_stride, written to out + s * sample_stride (floats).  p0 and p1 are [E, D] by edge id,
+ * rows D floats apart, as stag_agg_fwd takes them.
+ *   Per edge, the column id, the edge id, the position, the lane's 4 values of p0[e, :] and of p1[e, :] (exponentiated
+ *   there, once, when spec.p1_log), the source scale and the row are read ONCE; only the Philox block is drawn per
+ *   sample.  The parameter rows take 16-byte loads when D % 4 == 0 and both tables are 16-byte aligned, else the scalar
+ *   row forms; the bits are the same.  The weights are stag_agg_fwd's for the same spec at the sample's offset,
+ *   bit for bit.  The sums follow the plan-order rule of stag_agg_fwd_w1 and stag_agg_fwd_mc_edge above (blocks of 4
+ *   consecutive positions that start at +0, folded in order, Kahan-compensated in long units; a long row's segments leave
+ *   their partials in plan->workspace and are added in segment order by a second small launch, per sample): no atomics,
+ *   results are run-to-run bit-identical, and a sample's bits do not depend on the samples that share its pass.
+ *   seg_counters are not used; plan->xcd_order is ignored (plan order), which changes no bit.
+ *   Kinds NORMAL | UNIFORM, optional relu.  Any D >= 1 (D % 4 != 0: scalar row forms); channels past 256 go to further
+ *   channel tiles.  plan->workspace must hold stag_plan_workspace_bytes(n_seg, 4 * D, 0) bytes.
+ *   STAG_ENOSYS — the caller loops over stag_agg_fwd: in_norm; ldx == 0 (a broadcast row); chunk_base != 0; kind
+ *   BERNOULLI; a launch across a 2^32 boundary of the global position.  STAG_EINVAL: a NULL csr / x / spec / out / p0
+ *   (p0, p1: of a graph with edges — the per-edge arrays of a graph without edges have no address);
+ *   D <= 0; 0 < ldx < D; ldo < D; n_samples < 1; offset_stride < 0; n_samples > 1 with sample_stride < n_dst * ldo; kind
+ *   NONE / EXPLICIT; a param_mode other than PER_EDGE (PER_EDGE1 is stag_agg_fwd_mc_edge's, SCALAR / PER_CHANNEL are
+ *   stag_agg_fwd_mc's); deriv != 0; unknown reduce; the counter bounds of stag_agg_fwd; a plan without units.
+ *   STAG_ENOMEM: workspace too small.  Every argument is checked before any device work.                            */
+int stag_agg_fwd_mc_pedge(const stag_csr* csr, const stag_plan* plan, const float* x, int64_t ldx, int32_t D,
+                          const stag_noise_spec* spec, int32_t n_samples, int64_t offset_stride, int32_t reduce,
+                          const float* src_scale, const float* dst_scale, float* out, int64_t ldo,
+                          int64_t sample_stride, void* stream);
+
 /* w[eid, k] for every edge of the shard: what the reference keeps in
  * `self._edge_weight_sample` (stag/layers.py:107). relu and in_norm applied.
  * plan (may be NULL): the units bound what one team walks, so a hub row does not serialise.

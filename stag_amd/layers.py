@@ -155,11 +155,11 @@ class StagLayer(torch.nn.Module):
         w = self._descriptor(graph, dn, dist, relu=self.relu, in_norm=self.norm, differentiable=live, seed=gen.seed,
                              offset=gen.offset, epoch=gen.device_epoch)
         if w.param_mode > _lib.PARAM_PER_CHANNEL:
-            # amortised [E, 1] parameters batch on a base layer whose noise width is the feature width
-            # (stag_agg_fwd_mc_edge); GAT (width = heads) and [E, Dn] parameters keep the loop
+            # amortised [E, 1] and [E, Dn] parameters batch on a base layer whose noise width is the feature width
+            # (stag_agg_fwd_mc_edge, stag_agg_fwd_mc_pedge); GAT (width = heads, [E, H] parameters) keeps the loop
             from . import ops as _ops
-            if (w.param_mode != _lib.PARAM_PER_EDGE1 or isinstance(self.base_layer, GAT)
-                    or _ops.mc_edge_why_not(feat, w, graph) is not None):
+            why_not = _ops.mc_edge_why_not if w.param_mode == _lib.PARAM_PER_EDGE1 else _ops.mc_pedge_why_not
+            if isinstance(self.base_layer, GAT) or why_not(feat, w, graph) is not None:
                 return None
         gen.next_offset()
         w.n_samples, w.offset_stride = int(n_samples), int(offset_stride)

@@ -46,6 +46,18 @@ def _masked_mean(nll, mask):
     return nll[mask].mean()
 
 
+def _is_identity(module):
+    """True for a dense module that returns its input in its current mode: torch.nn.Identity, a Dropout that is off
+    (eval mode, or p == 0), or a Sequential of only such modules."""
+    if isinstance(module, torch.nn.Identity):
+        return True
+    if isinstance(module, torch.nn.Dropout):
+        return not module.training or module.p == 0
+    if isinstance(module, torch.nn.Sequential):
+        return all(_is_identity(m) for m in module)
+    return False
+
+
 class StagModel(torch.nn.Module):
     def __init__(self, layers: List[torch.nn.Module], likelihood: Likelihood = None,
                  kl_scaling=1.0):
@@ -76,20 +88,25 @@ class StagModel(torch.nn.Module):
         data and its noise fixed (every `*_mle` script), the batched aggregation needs no backward at all — the dense
         transform differentiates through the S outputs; with a learned (`vi=True`) first layer or an input that carries
         a gradient the forward is still batched and the backward is the loop's per-sample passes (ops._AggregateMC; for the
-        [E, 1] heads of an AmortizedDistribution(in, 1): stag_agg_fwd_mc_edge and ops._AggregateMCEdge)."""
+        [E, 1] heads of an AmortizedDistribution(in, 1): stag_agg_fwd_mc_edge and ops._AggregateMCEdge; for the [E, in]
+        heads of an AmortizedDistribution(in, in): stag_agg_fwd_mc_pedge and ops._AggregateMCPEdge).
+
+        "First" is the first layer behind a leading run of FeatOnlyLayers that are the identity in their current mode
+        (`FeatOnlyLayer(Dropout(0.5))` under eval(), as every `citation_*` script builds its models): those are applied
+        once, and the stochastic layer behind them sees the same input for every sample."""
         plan = self._mc_plan(graph, feat, n_samples)
         if plan is None:
             for _ in range(n_samples):
                 yield self._forward(graph, feat)
             return
-        gen, L, base, first_used, h1, g = plan
+        gen, L, base, first_used, h1, g, lead = plan
         h1 = h1.unbind(0)       # ONE autograd node for the S slices (S separate selects would each zero-fill [S, N, out])
-        first = self.layers[0]
+        first = self.layers[lead]
         for s in range(n_samples):
             gen.offset = (base + s * L + first_used) & _MASK64
             first.mc_select(s)          # the first layer's "last draw" is sample s, as after the loop's s-th pass
             h = h1[s]
-            for layer in self.layers[1:]:
+            for layer in self.layers[lead + 1:]:
                 h = layer(g, h)
             if gen.offset != (base + (s + 1) * L) & _MASK64:
                 if s == 0:
@@ -108,8 +125,14 @@ class StagModel(torch.nn.Module):
 
     def _mc_plan(self, graph, feat, n_samples):
         """(generator, offsets per sample, base offset, offsets of the first layer, [S, N, out] of the first layer,
-        graph) when the first layer's samples can be batched, else None."""
-        first = self.layers[0] if len(self.layers) else None
+        graph, index of that layer) when the first layer's samples can be batched, else None.  The first layer is the
+        one behind the leading FeatOnlyLayers that are the identity in their current mode."""
+        from .layers import FeatOnlyLayer
+        lead = 0
+        while (lead < len(self.layers) and isinstance(self.layers[lead], FeatOnlyLayer)
+               and _is_identity(self.layers[lead].layer)):
+            lead += 1
+        first = self.layers[lead] if lead < len(self.layers) else None
         if n_samples < 2 or not hasattr(first, "forward_mc") or getattr(self, "_mc_batching_off", False):
             return None
         stoch = [l for l in self.layers if hasattr(l, "forward_mc")]
@@ -123,11 +146,13 @@ class StagModel(torch.nn.Module):
             return None
         base = gen.offset
         graph = graph.local_var()
+        for layer in self.layers[:lead]:        # (the identity in this mode: applied once, for every sample)
+            feat = layer(graph, feat)
         h1 = first.forward_mc(graph, feat, n_samples, offset_stride=L)
         if h1 is None:
             gen.offset = base
             return None
-        return gen, L, base, first_used, h1, graph
+        return gen, L, base, first_used, h1, graph, lead
 
     def forward(self, graph, feat, n_samples=1, return_parameters=False):
         """Monte-Carlo average over `n_samples` noisy passes; noise stays on at eval time

@@ -1695,6 +1695,20 @@ def aggregate_mc(graph, x, noise, n_samples, offset_stride=1, reduce="sum", src_
                                           _f32c(src_scale), _f32c(dst_scale), seg_len)
         return _agg_fwd_mc_edge_raw(graph.csr, _f32c(x), noise, n_samples, offset_stride, _REDUCE[reduce],
                                     _f32c(src_scale), _f32c(dst_scale), seg_len)
+    if (n_samples > 1 and isinstance(noise, EdgeNoise) and noise.param_mode == _lib.PARAM_PER_EDGE
+            and mc_pedge_why_not(x, noise, graph) is None):
+        # amortised [E, D] parameters: the samples share the gather, both parameter rows (one exp of the log-scale) and
+        # the unit walk (stag_agg_fwd_mc_pedge); under autograd the backward is the loop's per-sample passes
+        # (_AggregateMCPEdge)
+        if needs_grad:
+            if noise.grad_params is not None:
+                p0, p1 = (torch.as_tensor(p, dtype=torch.float32, device=x.device) for p in noise.grad_params)
+            else:
+                p0 = p1 = None
+            return _AggregateMCPEdge.apply(x, p0, p1, graph, noise, int(n_samples), int(offset_stride), _REDUCE[reduce],
+                                           _f32c(src_scale), _f32c(dst_scale), seg_len)
+        return _agg_fwd_mc_pedge_raw(graph.csr, _f32c(x), noise, n_samples, offset_stride, _REDUCE[reduce],
+                                     _f32c(src_scale), _f32c(dst_scale), seg_len)
     if not fusable_mc or n_samples == 1:
         return torch.stack([one(s) for s in range(n_samples)], 0)
     if noise.dn != x.shape[1]:
@@ -1912,6 +1926,136 @@ class _AggregateMCEdge(torch.autograd.Function):
             if need_p:
                 d0 = e0 if d0 is None else d0 + e0
                 d1 = e1 if d1 is None else d1 + e1
+        dp = [None, None]
+        if need_p:
+            for i, d in enumerate((d0, d1)):
+                if ctx.needs_input_grad[1 + i]:
+                    shape = ctx.pshapes[i]
+                    dp[i] = d.sum_to_size(shape) if d.dim() >= len(shape) and shape != d.shape else d.reshape(shape)
+        return dx, dp[0], dp[1], None, None, None, None, None, None, None, None
+
+
+# ---- Monte-Carlo samples of amortised [E, D] edge noise (STAG_PARAM_PER_EDGE) from one pass ------------------------------
+# stag_agg_fwd_mc_pedge: S samples of a layer whose q_a is an AmortizedDistribution(in, in) — both layers of
+# `citation_rec/gcn`, evaluated and trained through model.forward / model.loss with n_samples > 1 (stag/models.py:45-55,
+# 67-68) — from one walk of the plan: per edge the ids, the lane's values of both [E, D] parameter rows (the log-scale
+# exponentiated once) and the row are read once, and only the Philox block is drawn per sample.  The switch ships True by
+# the usual rule: the batched launch is not slower than the loop of S stag_agg_fwd launches, beyond the spread of two
+# repeats, for EVERY case timed (profiles/r19/mc_pedge.txt; us per S samples, batched / loop, S = 2 | 4 | 8 | 16; two
+# repeats of the loop differ by 0.2-7.9, of the batched launch by 0.4-34):
+#   arxiv D = 128         Normal + log-scale 430 / 705 | 609 / 1386 | 1235 / 2750 | 2455 / 5481
+#                         Uniform            392 / 705 | 516 / 1387 | 1023 / 2744 | 2030 / 5472
+#   PPI batch D = 50      Normal + log-scale 199 / 289 | 252 / 566 | 500 / 1120 | 985 / 2219     Uniform 195 / 264 | 239 / 516 | 474 / 1021 | 940 / 2025
+#   PPI batch D = 256     Normal + log-scale 510 / 826 | 737 / 1631 | 1465 / 3237 | 2910 / 6452  Uniform 453 / 824 | 608 / 1628 | 1211 / 3232 | 2403 / 6441
+#   Cora-sized D = 1433   Normal + log-scale 134 / 181 | 167 / 352 | 342 / 733 | 668 / 1442      Uniform 127 / 170 | 154 / 331 | 313 / 685 | 617 / 1353
+# The narrowest win is S = 2 on the Cora-sized graph (43 us, 50 times the spread); a pass of 4 samples costs 0.37-0.47 of
+# four launches.  An inference StagModel.forward(n_samples = 16) of a citation_rec/gcn-shaped model (leading Dropout,
+# 1433 -> 16 -> 7) on the Cora-sized graph: 6.0 ms against 20.8 — q_a.condition() runs once instead of 16 times.  With the
+# switch off, PER_EDGE descriptors with n_samples > 1 take the loop.
+MC_PEDGE_FUSED = True
+
+
+def mc_pedge_why_not(x, noise, graph):
+    """The first reason ops.aggregate_mc does not hand x [N, D] with this descriptor ([E, D] parameters, n_samples > 1)
+    to stag_agg_fwd_mc_pedge, or None.  One clause per refusal of the entry point (include/stag_hip.h) and per path
+    without a form there; whatever gets a reason takes the stack of single calls."""
+    if not MC_PEDGE_FUSED:
+        return "switch"
+    if x.dim() != 2:
+        return "shape"
+    if x.stride(0) == 0:
+        return "broadcast row"
+    if x.dtype != torch.float32:
+        return "dtype"
+    if not isinstance(noise, EdgeNoise):
+        return "no descriptor"
+    if noise.param_mode != _lib.PARAM_PER_EDGE:
+        return "noise parameters"
+    if noise.dn != x.shape[1]:
+        return "noise width"
+    if noise.in_norm:
+        return "in-norm"
+    if noise.kind not in (_lib.NOISE_NORMAL, _lib.NOISE_UNIFORM):
+        return "kind"
+    if noise.deriv:
+        return "derivative selector"
+    if noise.chunk_base:
+        return "channel shard"
+    if (noise.pos_base & 0xFFFFFFFF) + noise.graph.number_of_edges() > (1 << 32):
+        return "position range"
+    if getattr(graph, "is_shard", False) or getattr(noise.graph, "is_shard", False):
+        return "shard"
+    if torch.compiler.is_compiling():
+        return "compiling"
+    if not x.is_cuda:
+        return "device"
+    return None
+
+
+def _agg_fwd_mc_pedge_raw(csrv, x, noise, n_samples, offset_stride, reduce, src_scale, dst_scale, seg_len):
+    """One stag_agg_fwd_mc_pedge call: [n_samples, n_dst, D].  Bound through ctypes only; the plan is walked in plan order,
+    or in the view's share order."""
+    D = x.shape[1]
+    dev = _lib.require_device(x, csrv.indptr, src_scale, dst_scale)
+    out = torch.empty((n_samples, csrv.n_dst, D), dtype=torch.float32, device=dev)
+    if csrv.n_dst == 0:
+        return out
+    plan_t = csrv.plan(seg_len)
+    nbytes = _lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], 4 * D, 0) if plan_t is not None else 0
+    plan_c, _keep = _plan_struct(csrv, seg_len, (D + 255) // 256, nbytes, dev, plan_t=plan_t, width=None, share=D)
+    cs, spec = csrv.struct(), noise.spec()
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_agg_fwd_mc_pedge(
+            C.byref(cs), C.byref(plan_c) if plan_c is not None else None, _lib.ptr(x), x.stride(0), D,
+            C.byref(spec), n_samples, offset_stride, reduce, _lib.ptr(src_scale), _lib.ptr(dst_scale),
+            _lib.ptr(out), D, csrv.n_dst * D, _lib.stream_of(dev))
+    _lib.check(rc, "stag_agg_fwd_mc_pedge")
+    return out
+
+
+class _AggregateMCPEdge(torch.autograd.Function):
+    """S Monte-Carlo samples of one aggregation with [E, D] noise parameters, with gradients: the forward is ONE batched
+    pass (stag_agg_fwd_mc_pedge), the backward the per-sample passes of the sequential loop, on the kernels _AggregateVI
+    chooses for [E, D] parameters — stag_agg_bwd on csr_t for dx, and both [E, D] parameter gradients from one
+    stag_agg_bwd_w call.  dx and the parameter gradients are summed over the samples in place.  Sample s draws at
+    offset + s * stride, so values and gradients are those of the loop.  Nothing beyond the gradients themselves is
+    [E, D]-sized."""
+
+    @staticmethod
+    def forward(ctx, x, p0, p1, graph, noise, n_samples, stride, reduce, src_scale, dst_scale, seg_len):
+        x = _f32c(x)
+        out = _agg_fwd_mc_pedge_raw(graph.csr, x, noise, n_samples, stride, reduce, src_scale, dst_scale, seg_len)
+        ctx.graph, ctx.noise, ctx.S, ctx.stride, ctx.reduce, ctx.seg_len = _owner(graph), noise, n_samples, stride, reduce, seg_len
+        ctx.pshapes = None if p0 is None else (p0.shape, p1.shape)
+        ctx.save_for_backward(x, src_scale, dst_scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        import copy
+        x, src_scale, dst_scale = ctx.saved_tensors
+        graph, D = ctx.graph, x.shape[1]
+        g_all = _f32c(grad_out)
+        dvec = dst_scale
+        if ctx.reduce == _lib.REDUCE_MEAN:
+            inv = 1.0 / graph.csr.degrees.clamp(min=1).to(torch.float32)
+            dvec = inv if dvec is None else dvec * inv
+        need_x = ctx.needs_input_grad[0]
+        need_p = ctx.pshapes is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        dx = d0 = d1 = None
+        for s_i in range(ctx.S):
+            nz = copy.copy(ctx.noise)
+            nz.offset = (ctx.noise.offset + s_i * ctx.stride) & _MASK64
+            spec = _noise_spec(nz, in_norm=0)
+            g = g_all[s_i]
+            if need_x:
+                dxs, _, _ = _agg_bwd_raw(graph.csr_t, g, D, spec, dvec, src_scale, ctx.seg_len, False)
+                dx = dxs if dx is None else dx.add_(dxs)
+            if need_p:
+                gg = (g if dvec is None else g * dvec.unsqueeze(1)).contiguous()
+                e0, e1 = _bwd_w_raw(graph.csr, x, gg, D, src_scale, spec=_targs_or_c(spec), both=True, seg_len=ctx.seg_len)
+                d0 = e0 if d0 is None else d0.add_(e0)
+                d1 = e1 if d1 is None else d1.add_(e1)
         dp = [None, None]
         if need_p:
             for i, d in enumerate((d0, d1)):
