@@ -403,7 +403,11 @@ int stag_normal_tables(float* rad, float* cosv, float* sinv, void* stream);
  *           94-96, 100-108) / GraphSAGE mean (stag/zoo/graph_sage.py:70-73).
  * `norm_scale_out` (may be NULL; written only when spec.in_norm): s[M, D], kept for
  * the backward pass.  `plan` may be NULL: one unit per row, in row order, no split.
- * ldx == 0 gathers one broadcast row (sum of edge data, stag/layers.py:12-15).   */
+ * ldx == 0 gathers one broadcast row (sum of edge data, stag/layers.py:12-15).
+ * The row stride of the gathered table travels to the kernels as 32 bits of bytes: ldx * 4 >= 2^32 (ldg for
+ * stag_agg_bwd, stag_agg_bwd_edge and stag_agg_bwd_dp below) is STAG_ENOSYS, here and in stag_agg_fwd_mc, before
+ * any device work — the caller packs the rows (one contiguous copy).  Any smaller stride, any n_src and any extent
+ * are taken: the entry point picks 32-bit or 64-bit addresses itself (csrc/entry_args.hpp: agg_forms).   */
 int stag_agg_fwd(const stag_csr* csr, const stag_plan* plan, const float* x,
                  int64_t ldx, int32_t D, const stag_noise_spec* spec,
                  int32_t reduce, const float* src_scale, const float* dst_scale,
@@ -437,6 +441,7 @@ int stag_agg_fwd_mc(const stag_csr* csr, const stag_plan* plan, const float* x, 
  * scalar parameter sum over k as well.  dp0_rows == dp1_rows == NULL: dx only (= stag_agg_fwd on
  * csr_t).  With the dp outputs: kind NORMAL | UNIFORM, param_mode SCALAR | PER_CHANNEL, in_norm 0;
  * the plan's workspace must hold stag_plan_workspace_bytes(n_seg, 3 * D, 0) bytes.
+ * ldg * 4 >= 2^32: STAG_ENOSYS (see stag_agg_fwd); the same holds for stag_agg_bwd_dp and stag_agg_bwd_edge.
  * Replaces the three autograd passes over [E, D] tensors of the reference's backward.        */
 int stag_agg_bwd(const stag_csr* csr_t, const stag_plan* plan_t, const float* g, int64_t ldg,
                  int32_t D, const stag_noise_spec* spec, const float* g_scale,

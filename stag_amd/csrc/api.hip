@@ -948,6 +948,11 @@ static int agg_common(const stag_csr* csr, const stag_plan* plan, const float* x
   if (rc) return rc;
   if (D <= 0 || (ldx != 0 && ldx < D) || ldo < D) return STAG_EINVAL;
   if (reduce != STAG_REDUCE_SUM && reduce != STAG_REDUCE_MEAN) return STAG_EINVAL;
+  // 32-bit byte offsets + 24-bit multiplies when everything fits, else 64-bit addressing; a stride past 32 bits of bytes
+  // is refused (a.ldxb)
+  AggForms forms;
+  rc = agg_forms(csr->n_src, csr->n_edges, ldx, D, forms);
+  if (rc) return rc;
   if (csr->n_dst == 0) return STAG_OK;        // no row, nothing to write (an output of no rows has no address: a shard
                                               // whose cut left it without rows still makes the call)
   // ldx == 0: one broadcast row; out may be NULL when only the in-norm factor (or the edge gradients) is wanted
@@ -959,16 +964,7 @@ static int agg_common(const stag_csr* csr, const stag_plan* plan, const float* x
   a.n_rows = csr->n_dst;
   a.x = x; a.ldx = ldx; a.D = D;
   a.ldxb = (uint32_t)(ldx * 4); a.ldwb = (uint32_t)D * 4u;
-  {
-    // 32-bit byte offsets + 24-bit multiplies when everything fits, else 64-bit addressing
-    const uint64_t xbytes = (uint64_t)csr->n_src * (uint64_t)ldx * 4u;
-    const uint64_t wbytes = (uint64_t)csr->n_edges * (uint64_t)D * 4u;   // (upper bound when grouped)
-    const bool x_narrow = xbytes < (1ull << 32) && csr->n_src < (1 << 24) && (uint64_t)ldx * 4u < (1u << 24);
-    const bool w_narrow = wbytes < (1ull << 32) && csr->n_edges < (1 << 24) && (uint64_t)D * 4u < (1u << 24);
-    a.wide = (x_narrow ? 0 : 1) | (w_narrow ? 0 : 2);
-    a.x_bytes = x_narrow ? (uint32_t)(ldx == 0 ? (uint64_t)D * 4u : xbytes) : 0u;
-    a.idx_bytes = csr->n_edges < (1 << 30) ? (uint32_t)csr->n_edges * 4u : 0u;
-  }
+  a.wide = (int32_t)forms.wide; a.x_bytes = forms.x_bytes; a.idx_bytes = forms.idx_bytes;
   fill_spec(a, spec, spec->deriv);
   a.in_norm = spec->in_norm;
   a.wgroup = (spec->kind == STAG_NOISE_EXPLICIT && spec->group > 1) ? spec->group : 1;

@@ -27,6 +27,31 @@ inline int narrow_rows(int64_t n_src, int64_t ldx, int32_t D, uint32_t esize, ui
   return !narrow && stride >= (1ull << 32) ? STAG_ENOSYS : STAG_OK;
 }
 
+// The same decision for the kernels of agg_common (api.hip: stag_agg_fwd, stag_agg_fwd_mc, stag_agg_bwd, stag_agg_bwd_edge,
+// stag_agg_bwd_dp), which also read per-edge rows of D floats ([E, D] weights or parameters, by edge id or CSR position):
+//   wide bit 0: x takes 64-bit addresses (n_src >= 2^24 rows, a stride >= 2^24 bytes, or n_src * ldx * 4 >= 2^32 bytes)
+//   wide bit 1: the per-edge rows do (n_edges >= 2^24, D * 4 >= 2^24, or n_edges * D * 4 >= 2^32; an upper bound when grouped)
+//   x_bytes: the extent behind x's buffer descriptor in the narrow form (n_src rows of ldx floats; ldx == 0: the one
+//            broadcast row of D floats), else 0
+//   idx_bytes: the extent of the column ids behind theirs, 0 from 2^30 edges on
+// The row stride travels as 32 bits of bytes in every form: one of 2^32 bytes or more is refused (STAG_ENOSYS), as
+// narrow_rows refuses it.
+struct AggForms {
+  uint32_t wide, x_bytes, idx_bytes;
+};
+inline int agg_forms(int64_t n_src, int64_t n_edges, int64_t ldx, int32_t D, AggForms& f) {
+  f = AggForms{};
+  if (ldx >= (1ll << 30)) return STAG_ENOSYS;
+  const uint64_t xbytes = (uint64_t)n_src * (uint64_t)ldx * 4u;
+  const uint64_t wbytes = (uint64_t)n_edges * (uint64_t)D * 4u;
+  const bool x_narrow = xbytes < (1ull << 32) && n_src < (1 << 24) && (uint64_t)ldx * 4u < (1u << 24);
+  const bool w_narrow = wbytes < (1ull << 32) && n_edges < (1 << 24) && (uint64_t)D * 4u < (1u << 24);
+  f.wide = (x_narrow ? 0u : 1u) | (w_narrow ? 0u : 2u);
+  f.x_bytes = x_narrow ? (uint32_t)(ldx == 0 ? (uint64_t)D * 4u : xbytes) : 0u;
+  f.idx_bytes = n_edges < (1 << 30) ? (uint32_t)n_edges * 4u : 0u;
+  return STAG_OK;
+}
+
 // lanes per row: the smallest power of two >= min_lanes that covers nchunk chunks, capped at a wave
 inline int lanes_for(int nchunk, int min_lanes) {
   int lpe = min_lanes;

@@ -30,7 +30,14 @@ def _f32c(t):
         return None
     if t.dtype != torch.float32:
         t = t.float()
-    return t.contiguous()
+    t = t.contiguous()
+    if t.dim() == 2 and t.stride(0) >= _MAX_ROW_STRIDE:
+        # one row is contiguous whatever stride its view carries; the library takes 32 bits of bytes (STAG_ENOSYS past them)
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
+_MAX_ROW_STRIDE = 1 << 30      # floats: the aggregation entry points refuse a row stride of 2^32 bytes or more
 
 
 # A noise description travels to the library in one of two forms: the ctypes `stag_noise_spec`, or — when
