@@ -736,7 +736,10 @@ struct AggTeam {
           float e0 = 0.f, e1 = 0.f;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const float gx = R.xv[j][q] * XO.v[q];
+            float gx = R.xv[j][q] * XO.v[q];
+            // past the row's end the descriptor load holds the NEXT row's floats (bufrow4) and the own row 0: a
+            // non-finite neighbour would make 0 * inf = NaN of a term that is not there
+            if constexpr (!VEC) gx = (k0 + q < a.D) ? gx : 0.f;
             e0 = __builtin_fmaf(g0[q], gx, e0);
             e1 = __builtin_fmaf(g1[q], gx, e1);
           }
