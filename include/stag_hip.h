@@ -642,6 +642,37 @@ int stag_agg_bwd_w(const stag_csr* csr, const stag_plan* plan, const float* x, i
                    const float* src_scale, const stag_noise_spec* spec, int32_t reduce_k,
                    float* dw, float* dw1, int64_t ldw, void* stream);
 
+/* ---- Per-edge parameter gradients of a Monte-Carlo batch from one pass (the backward of stag_agg_fwd_mc_edge and
+ * stag_agg_fwd_mc_pedge with respect to the amortised parameters), additive in v19 ----
+ * On the forward (destination-major) csr:
+ *   val_s[p, k]    = (sscale[u_p] * x[u_p, k]) * (gscale[v] * g[s * g_sample_stride + v * ldg + k])   (NULL scale: factor left out)
+ *   dw_i[eid_p, k] = sum_{s = 0 .. n_samples - 1} D_i,s[p, k] * val_s[p, k]                           i = 0, 1
+ * D_0,s and D_1,s are the two derivatives of the draw at spec.offset + s * offset_stride (mod 2^64, plus *spec.epoch):
+ * exactly what stag_agg_bwd_w writes to dw and dw1 for that spec when dw1 != NULL; relu, p1_log, pos_base, csr.nidx and
+ * csr.eid are honoured as there.  reduce_k != 0: the outputs are [E, 1], the sum over k as well, in stag_agg_bwd_w's
+ * fixed order.  dw1 may be NULL.
+ *   Per edge, the column id, the edge id, the position, the source scale, the row x[u] and the lane's 4 values of
+ *   p0[e, :] and p1[e, :] (or the two scalars of an [E, 1] pair; exponentiated there, once, when spec.p1_log) are read
+ *   ONCE; the n_samples gradient rows are the unit's own rows; only the Philox block is drawn per sample.  Samples are
+ *   added in increasing s, starting from sample 0's term (not from +0): with n_samples == 1 and g_scale == NULL the
+ *   outputs are stag_agg_bwd_w's bit for bit.  Up to 4 samples ride in a pass; more run as further passes (4, then 2,
+ *   then 1) inside the call, each adding to what the previous pass left for the same edge.  No atomics; results are
+ *   run-to-run bit-identical.  Every gradient table is written once per pass and, within a pass, never read back.
+ *   Kinds NORMAL | UNIFORM, optional relu.  param_mode STAG_PARAM_PER_EDGE ([E, D] tables, rows D floats apart) with
+ *   reduce_k == 0, or STAG_PARAM_PER_EDGE1 ([E, 1]) with reduce_k != 0.  Any D >= 1: D % 4 != 0, an unaligned pointer or
+ *   an unaligned stride take the scalar row forms, with the same bits.  Any n_samples >= 1.  plan may be NULL.
+ *   STAG_ENOSYS — the caller keeps the loop over stag_agg_bwd_w: in_norm; ldx == 0 (a broadcast row); chunk_base != 0; a
+ *   launch across a 2^32 boundary of the global position; ldx * 4 or ldg * 4 >= 2^32.  STAG_EINVAL: a NULL csr / x / g /
+ *   spec / dw0 / p0 (p0, p1: of a graph with edges); D <= 0; 0 < ldx < D; ldg < D; ldw < (reduce_k ? 1 : D);
+ *   n_samples < 1; offset_stride < 0; n_samples > 1 with g_sample_stride < n_dst * ldg; kind NONE / EXPLICIT / BERNOULLI;
+ *   SCALAR / PER_CHANNEL parameters (stag_agg_bwd_dp's); PER_EDGE with reduce_k, or PER_EDGE1 without it; deriv != 0; the
+ *   counter bounds of stag_agg_fwd; a plan without units.  Every argument is checked before any device work; a graph
+ *   without rows or edges returns STAG_OK after the checks.                                                          */
+int stag_agg_bwd_w_mc(const stag_csr* csr, const stag_plan* plan, const float* x, int64_t ldx, const float* g,
+                      int64_t ldg, int64_t g_sample_stride, int32_t D, const float* src_scale, const float* g_scale,
+                      const stag_noise_spec* spec, int32_t n_samples, int64_t offset_stride, int32_t reduce_k,
+                      float* dw0, float* dw1, int64_t ldw, void* stream);
+
 /* per-graph readout of a batched graph: out[b,:] = sum|mean of x[offsets[b]:offsets[b+1],:]
  * (dgl.sum_nodes / dgl.mean_nodes, stag/layers.py:165,177)                      */
 int stag_segment_reduce(const float* x, int64_t ldx, int32_t D,

@@ -1889,7 +1889,9 @@ class _AggregateMCEdge(torch.autograd.Function):
     pass (stag_agg_fwd_mc_edge), the backward the per-sample transposed passes of the sequential loop, on the kernels
     _AggregateVI chooses for [E, 1] parameters — stag_agg_bwd_edge (dx and both per-edge gradients from one pass) for
     D <= 256, else stag_agg_bwd + stag_agg_bwd_w.  dx and the [E, 1] gradients are summed over the samples.  Sample s
-    draws at offset + s * stride, so values and gradients are those of the loop.  Nothing [E, D]-sized is saved."""
+    draws at offset + s * stride, so values and gradients are those of the loop.  Nothing [E, D]-sized is saved.
+    Where mc_bwd_why_not allows (MC_BWD_FUSED; x without a gradient, or D > 256) both [E, 1] gradients of all samples
+    come from one stag_agg_bwd_w_mc call instead; dx stays the loop's."""
 
     @staticmethod
     def forward(ctx, x, p0, p1, graph, noise, n_samples, stride, reduce, src_scale, dst_scale, seg_len):
@@ -1913,24 +1915,30 @@ class _AggregateMCEdge(torch.autograd.Function):
         need_x = ctx.needs_input_grad[0]
         need_p = ctx.pshapes is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
         dx = d0 = d1 = None
-        for s_i in range(ctx.S):
+        # both [E, 1] gradients of all S samples from one pass (stag_agg_bwd_w_mc) where x needs no gradient or D > 256;
+        # with dx at D <= 256 stag_agg_bwd_edge already takes all three from one gather per sample
+        fused = need_p and mc_bwd_why_not(x, ctx.noise, graph, need_x) is None
+        if fused:
+            d0, d1 = _bwd_w_mc_raw(graph.csr, x, g_all, D, src_scale, dvec, _targs_or_c(_noise_spec(ctx.noise, in_norm=0)),
+                                   ctx.S, ctx.stride, reduce_k=True, seg_len=ctx.seg_len)
+        for s_i in range(ctx.S if (need_x or not fused) else 0):
             nz = copy.copy(ctx.noise)
             nz.offset = (ctx.noise.offset + s_i * ctx.stride) & _MASK64
             spec = _targs_or_c(_noise_spec(nz, in_norm=0))
             g = g_all[s_i]
             dxs = e0 = e1 = None
-            if need_p and D <= 256:
+            if need_p and not fused and D <= 256:
                 dxs, e0, e1 = _agg_bwd_edge_raw(graph.csr_t, g, x, D, spec, dvec, src_scale, ctx.seg_len, want_dx=need_x)
             else:
                 if need_x:
                     dxs, _, _ = _agg_bwd_raw(graph.csr_t, g, D, spec, dvec, src_scale, ctx.seg_len, False)
-                if need_p:
+                if need_p and not fused:
                     gg = (g if dvec is None else g * dvec.unsqueeze(1)).contiguous()
                     e0, e1 = _bwd_w_raw(graph.csr, x, gg, D, src_scale, spec=spec, reduce_k=True, both=True,
                                         seg_len=ctx.seg_len)
             if need_x:
                 dx = dxs if dx is None else dx + dxs
-            if need_p:
+            if need_p and not fused:
                 d0 = e0 if d0 is None else d0 + e0
                 d1 = e1 if d1 is None else d1 + e1
         dp = [None, None]
@@ -2026,7 +2034,8 @@ class _AggregateMCPEdge(torch.autograd.Function):
     chooses for [E, D] parameters — stag_agg_bwd on csr_t for dx, and both [E, D] parameter gradients from one
     stag_agg_bwd_w call.  dx and the parameter gradients are summed over the samples in place.  Sample s draws at
     offset + s * stride, so values and gradients are those of the loop.  Nothing beyond the gradients themselves is
-    [E, D]-sized."""
+    [E, D]-sized.  Where mc_bwd_why_not allows (MC_BWD_FUSED) both [E, D] gradients of all samples come from one
+    stag_agg_bwd_w_mc call instead; dx stays the loop's."""
 
     @staticmethod
     def forward(ctx, x, p0, p1, graph, noise, n_samples, stride, reduce, src_scale, dst_scale, seg_len):
@@ -2050,7 +2059,13 @@ class _AggregateMCPEdge(torch.autograd.Function):
         need_x = ctx.needs_input_grad[0]
         need_p = ctx.pshapes is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
         dx = d0 = d1 = None
-        for s_i in range(ctx.S):
+        # both [E, D] gradients of all S samples from one pass (stag_agg_bwd_w_mc): dvec rides along as g_scale, so no
+        # [N, D] product is formed and each gradient table is written once
+        fused = need_p and mc_bwd_why_not(x, ctx.noise, graph, need_x) is None
+        if fused:
+            d0, d1 = _bwd_w_mc_raw(graph.csr, x, g_all, D, src_scale, dvec, _targs_or_c(_noise_spec(ctx.noise, in_norm=0)),
+                                   ctx.S, ctx.stride, reduce_k=False, seg_len=ctx.seg_len)
+        for s_i in range(ctx.S if (need_x or not fused) else 0):
             nz = copy.copy(ctx.noise)
             nz.offset = (ctx.noise.offset + s_i * ctx.stride) & _MASK64
             spec = _noise_spec(nz, in_norm=0)
@@ -2058,7 +2073,7 @@ class _AggregateMCPEdge(torch.autograd.Function):
             if need_x:
                 dxs, _, _ = _agg_bwd_raw(graph.csr_t, g, D, spec, dvec, src_scale, ctx.seg_len, False)
                 dx = dxs if dx is None else dx.add_(dxs)
-            if need_p:
+            if need_p and not fused:
                 gg = (g if dvec is None else g * dvec.unsqueeze(1)).contiguous()
                 e0, e1 = _bwd_w_raw(graph.csr, x, gg, D, src_scale, spec=_targs_or_c(spec), both=True, seg_len=ctx.seg_len)
                 d0 = e0 if d0 is None else d0.add_(e0)
@@ -2070,6 +2085,99 @@ class _AggregateMCPEdge(torch.autograd.Function):
                     shape = ctx.pshapes[i]
                     dp[i] = d.sum_to_size(shape) if d.dim() >= len(shape) and shape != d.shape else d.reshape(shape)
         return dx, dp[0], dp[1], None, None, None, None, None, None, None, None
+
+
+# ---- The per-edge parameter gradients of a Monte-Carlo batch from one pass ---------------------------------------------
+# stag_agg_bwd_w_mc: the parameter side of the backward of _AggregateMCEdge and _AggregateMCPEdge.  On the forward csr
+# everything a sample does not own is shared — x[u], the edge's parameters (one exp of a log-scale), the ids — the S
+# gradient rows are the unit's own rows, only the Philox block is drawn per sample, and the sum over samples happens in
+# registers: each gradient table is written once.  For [E, D] heads one call replaces S x (g * dvec pass + stag_agg_bwd_w +
+# two add_ passes); for [E, 1] heads it replaces S stag_agg_bwd_edge passes over csr_t where x needs no gradient (the first
+# layer of every model) and S stag_agg_bwd_w passes at D > 256.  dx keeps the loop's per-sample passes in every case.
+# Compiler's report (csrc/_obj/agg_bwd_w_mc.remarks): 0 bytes of scratch in all 42 instantiations; a pass of 4 samples takes
+# 235-238 VGPRs (2 waves per SIMD), of 2 samples 185-190 (2), of 1 sample 159-160 (3); teams of one lane 122-202.
+# Measured (profiles/r21/mc_bwd.txt; us per backward of S samples, batched / loop, S = 2 | 4; both parameters live, x
+# without a gradient; two repeats of the loop differ by 0.5-47, of the batched call by 0.1-60):
+#   [E, D] heads   arxiv D = 128        Normal + log-scale 1189 / 1928 | 1431 / 4518     Uniform 1063 / 1941 | 1212 / 4458
+#                  PPI batch D = 50     Normal + log-scale  532 /  920 |  596 / 2031     Uniform  513 /  921 |  577 / 2042
+#                  PPI batch D = 256    Normal + log-scale 1456 / 2467 | 1654 / 5747     Uniform 1276 / 2538 | 1455 / 5914
+#                  Cora-sized D = 1433  Normal + log-scale  965 / 1375 | 1202 / 2849     Uniform  954 / 1400 | 1154 / 2845
+#   [E, 1] heads   arxiv D = 128        Normal + log-scale  792 /  433 |  998 /  861     Uniform  766 /  423 |  984 /  853
+#                  PPI batch D = 50     Normal + log-scale  267 /  161 |  320 /  293     Uniform  256 /  144 |  312 /  258
+#                  PPI batch D = 256    Normal + log-scale  951 /  505 | 1180 / 1011     Uniform  921 /  448 | 1169 /  907
+#                  Cora-sized D = 1433  Normal + log-scale  399 /  537 |  565 / 1058     Uniform  410 /  535 |  617 / 1055
+# The peak allocation of a backward halves for [E, D] heads at S = 2 and is a third at S = 4 (arxiv: 1140 MB against 2280 |
+# 3420: the two gradient tables, without the loop's per-sample pair).
+# The switch ships False by the usual rule (True only if the batched call is not slower than the loop, beyond the spread
+# of two repeats, for EVERY case timed): every [E, D] case wins (0.69 of the loop at the narrowest, Cora-sized S = 2; 0.25-0.42
+# at S = 4) and so do [E, 1] heads past one channel tile, but [E, 1] heads at D <= 256 whose input carries no gradient
+# LOSE to the S stag_agg_bwd_edge passes in all 12 cases timed: arxiv D = 128, PPI batch D = 50 and D = 256, Normal with
+# log-scale and Uniform, S = 2 and S = 4 (by 27-473 us; 1.09-2.06 of the loop).  There a pass costs a fixed ~590 us at the
+# arxiv shape plus ~100 us per sample against the loop's ~215 us per sample: the walk of two edges at a time at 2 waves
+# per SIMD is bound by its dependent loads (ids, then rows), not by traffic.  With the switch off both nodes run the loop.
+MC_BWD_FUSED = False
+
+
+def mc_bwd_why_not(x, noise, graph, need_x):
+    """The first reason the backward of ops.aggregate_mc (_AggregateMCEdge, _AggregateMCPEdge) does not take the parameter
+    gradients of its samples from one stag_agg_bwd_w_mc call, or None.  One clause per refusal of the entry point
+    (include/stag_hip.h) and per path without a form there; whatever gets a reason keeps the per-sample loop.  need_x: x
+    needs a gradient too — then [E, 1] heads at D <= 256 keep stag_agg_bwd_edge, which takes dx and both gradients from
+    one gather per sample."""
+    if not MC_BWD_FUSED:
+        return "switch"
+    if x.dim() != 2:
+        return "shape"
+    if x.stride(0) == 0:
+        return "broadcast row"
+    if x.dtype != torch.float32:
+        return "dtype"
+    if not isinstance(noise, EdgeNoise):
+        return "no descriptor"
+    if noise.param_mode not in (_lib.PARAM_PER_EDGE1, _lib.PARAM_PER_EDGE):
+        return "noise parameters"
+    if noise.dn != x.shape[1]:
+        return "noise width"
+    if noise.in_norm:
+        return "in-norm"
+    if noise.kind not in (_lib.NOISE_NORMAL, _lib.NOISE_UNIFORM):
+        return "kind"
+    if noise.deriv:
+        return "derivative selector"
+    if noise.chunk_base:
+        return "channel shard"
+    if (noise.pos_base & 0xFFFFFFFF) + noise.graph.number_of_edges() > (1 << 32):
+        return "position range"
+    if getattr(graph, "is_shard", False) or getattr(noise.graph, "is_shard", False):
+        return "shard"
+    if noise.param_mode == _lib.PARAM_PER_EDGE1 and need_x and x.shape[1] <= 256:
+        return "one gather"
+    if torch.compiler.is_compiling():
+        return "compiling"
+    if not x.is_cuda:
+        return "device"
+    return None
+
+
+def _bwd_w_mc_raw(csrv, x, g_all, D, src_scale, g_scale, spec, n_samples, offset_stride, reduce_k=False,
+                  seg_len=DEFAULT_SEG_LEN, both=True):
+    """One stag_agg_bwd_w_mc call: (d/dp0, d/dp1) summed over the n_samples draws of spec, [E, D] or, with reduce_k,
+    [E, 1].  g_all: [n_samples, n_dst, D], contiguous.  Bound through ctypes only."""
+    dev = _lib.require_device(x, g_all, src_scale, g_scale)
+    cols = 1 if reduce_k else D
+    dw0 = torch.empty((csrv.n_edges, cols), dtype=torch.float32, device=dev)
+    dw1 = torch.empty_like(dw0) if both else None
+    if csrv.n_edges == 0 or csrv.n_dst == 0:
+        return dw0, dw1
+    plan_c, _keep = _plan_struct(csrv, seg_len, 1, 0, dev)
+    cs = csrv.struct()
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_agg_bwd_w_mc(C.byref(cs), C.byref(plan_c) if plan_c is not None else None,
+                                          _lib.ptr(x), x.stride(0), _lib.ptr(g_all), g_all.stride(-2), g_all.stride(0), D,
+                                          _lib.ptr(src_scale), _lib.ptr(g_scale), C.byref(spec), n_samples, offset_stride,
+                                          int(reduce_k), _lib.ptr(dw0), _lib.ptr(dw1), cols, _lib.stream_of(dev))
+    _lib.check(rc, "stag_agg_bwd_w_mc")
+    return dw0, dw1
 
 
 def materialize_noise(graph, noise, seg_len=DEFAULT_SEG_LEN):
