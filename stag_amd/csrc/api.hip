@@ -110,6 +110,16 @@ __device__ __forceinline__ void edge_w4_grad_p(const NoiseArgs& a, const PhiloxK
   else draw4_grad<kUniform>((uint32_t)gpos, ctr1_of(gpos, chunk), key, pa, pb, a.nflags, w, d0, d1);
 }
 
+// the standard Normal draws z of the edge at position p: draw4<kNormal> returns w = fma(scale, z, loc) of these
+__device__ __forceinline__ void edge_z4(const NoiseArgs& a, const PhiloxKey& key, int p, uint32_t chunk, float (&z)[4]) {
+  const int64_t gpos = a.pos_base + (a.nidx ? (int64_t)a.nidx[p] : (int64_t)p);
+  chunk += a.chunk_base;
+  uint32_t r[4];
+  philox4x32_10((uint32_t)gpos, ctr1_of(gpos, chunk), key, r);
+  box_muller(r[0], r[1], z[0], z[1]);
+  box_muller(r[2], r[3], z[2], z[3]);
+}
+
 __device__ __forceinline__ void edge_w4(const NoiseArgs& a, int p, int64_t ed, uint32_t chunk,
                                         float (&w)[4]) {
   const int k0 = (int)chunk * 4;
@@ -227,7 +237,7 @@ __device__ __forceinline__ void sample_kl_body(const SampleKlArgs& b) {
   const int nchunk = (a.Dn + 3) / 4;
   const int ntile = EDGE ? (nchunk + LPE - 1) / LPE : 1;
   const PhiloxKey key = resolve_epoch(a.key);
-  const bool logs = (a.nflags & kFlagLogScale) != 0;
+  const bool logs = (a.nflags & kFlagLogScale) != 0, relu = (a.nflags & kFlagRelu) != 0;
   // the mixture, read uniformly: c_j = logw_j - log s_j, m_j, 1 / s_j
   float mc[KMAX], mm[KMAX], mi[KMAX];
 #pragma unroll
@@ -250,14 +260,21 @@ __device__ __forceinline__ void sample_kl_body(const SampleKlArgs& b) {
       const uint32_t chunk = (EDGE ? tile : (int)blockIdx.y) * LPE + c;
       const int k0 = (int)chunk * 4;
       if (k0 >= a.Dn) continue;
-      float pa[4], pb[4], w[4], d0[4], d1[4];
+      float pa[4], pb[4], z[4], w[4];
       edge_params4(a, ed, k0, pa, pb);
-      edge_w4_grad_p(a, key, p, chunk, pa, pb, w, d0, d1);
+      edge_z4(a, key, p, chunk, z);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
+        w[q] = __builtin_fmaf(pb[q], z[q], pa[q]);            // draw4's sample, bit for bit
+        if (relu) w[q] = fmaxf(w[q], 0.0f);
         const bool in = k0 + q < a.Dn;          // (a tail channel has no parameters: whatever it computes is dropped)
         const float is = __builtin_amdgcn_rcpf(pb[q]);
-        const float u = (w[q] - pa[q]) * is;
+        // u = (w - loc) / s.  An unclipped w = fma(s, z, loc) is ROUNDED: rebuilt from it, u carries |loc| / s roundings
+        // of w (s = 1e-4 |loc|: 1e-3 of u), and the gradients would be what is left when u / s and (u^2 - 1) / s cancel
+        // against dt/dw.  The draw is at hand, so an unclipped element takes u = z and the cancelled forms below; a
+        // clipped w is exactly 0 and keeps the rebuilt u.
+        const bool open = !(relu && !(w[q] > 0.0f));
+        const float u = open ? z[q] : (w[q] - pa[q]) * is;
         float e[KMAX], mx = -INFINITY;
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
@@ -279,11 +296,15 @@ __device__ __forceinline__ void sample_kl_body(const SampleKlArgs& b) {
         const float t = (-__logf(pb[q]) - 0.5f * (u * u)) - (mx + __logf(S));
         val += in ? t : 0.f;
         if (b.want_grad) {
-          const float A = u * is;                                        // (w - loc) / s^2
-          const float G = R * __builtin_amdgcn_rcpf(S) - A;              // dt/dw
-          const float B = (u * u - 1.0f) * (logs ? 1.0f : is);           // dt/ds | dt/dlog s at fixed w
-          const float g0 = in ? A + G * d0[q] : 0.f;
-          const float g1 = in ? B + G * d1[q] : 0.f;
+          // dt/dloc = A + (rs - A) dw/dloc, dt/ds = B + (rs - A) dw/ds with A = u / s, B = (u^2 - 1) / s (x s for a
+          // log-scale) and rs = R / S.  Unclipped (dw/dloc = 1, dw/ds = z): A cancels and B + (rs - A) z = rs z - 1 / s
+          // exactly, so the large terms are never formed.  Clipped (dw/d. = 0): A and B alone.
+          const float rs = R * __builtin_amdgcn_rcpf(S);
+          const float one = logs ? 1.0f : is;
+          const float g0v = open ? rs : u * is;
+          const float g1v = open ? rs * (logs ? z[q] * pb[q] : z[q]) - one : (u * u - 1.0f) * one;
+          const float g0 = in ? g0v : 0.f;
+          const float g1 = in ? g1v : 0.f;
           if (EDGE) { e0 += g0; e1 += g1; }
           else { a0[q] += g0; a1[q] += g1; }
         }
