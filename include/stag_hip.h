@@ -744,6 +744,42 @@ int stag_normal_kl_bwd(const float* loc, const float* log_scale, int64_t n, cons
                        const float* p_scale, const float* g, float* dloc, float* dlog_scale, float* dp_loc,
                        float* dp_scale, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the wide edge embedding of amortised per-edge parameters (an AmortizedDistribution(in, out) with out > 1: both
+ * layers of citation_rec/gcn, the second layer of citation_rec/gat), additive in v19 ----
+ * The hidden layer of the per-edge MLP over the two projected node tables ps, pd (the Linear's source and destination
+ * halves, the bias on the destination half), [E, hidden] by edge id:
+ *     h[e, k] = SiLU(ps[src[e], k] + pd[dst[e], k])
+ *     pre = ps + pd rounded to fp32;  sg = 1 / (1 + expf(-pre));  SiLU(pre) = pre * sg;  SiLU'(pre) = sg * (1 + pre * (1 - sg))
+ *   — the function stag_edge_mlp_fwd computes for hidden <= 8, at any width.
+ * stag_edge_embed_fwd: edge-parallel over the COO arrays src, dst [n_edges] (trusted to be row ids of ps / pd, as
+ *   stag_edge_mlp_fwd trusts them); a team of lanes per edge, 4 channels a lane, channels past 256 in further channel
+ *   tiles; 16-byte loads and stores when hidden % 4 == 0 and the rows are 16-byte aligned, scalar forms otherwise.
+ *   ldps, ldpd, ldh: row strides in floats (>= hidden: the two halves of one [N, 2 hidden] table are such rows).
+ * stag_edge_embed_bwd: the gradient of ONE of the two tables from the incoming gradient g [n_edges, hidden] (row
+ *   stride ldg, by edge id), over the CSR view whose rows are that table's endpoint:
+ *     d_own[r, k] = sum_{p in row r} g[E_p, k] * SiLU'(own[r, k] + other[view.indices[p], k]),  E_p = view.eid ? view.eid[p] : p
+ *   The destination-major view with own = pd, other = ps gives d pd; the source-major view with own = ps, other = pd
+ *   gives d ps.  The pre-activation is formed again from the two tables: nothing [n_edges, hidden] is saved by the
+ *   forward or formed here.  The sums follow the plan-order rule of stag_agg_fwd_w1 above: one team per unit of `plan`
+ *   (may be NULL: one unit per row), the own row loaded once per unit, blocks of 4 consecutive positions summed from
+ *   +0 and folded in order, Kahan-compensated in units of more than 16 edges; segments of long rows leave fp32 partial
+ *   sums in plan->workspace (>= stag_plan_workspace_bytes(n_seg, hidden, 0)), added in segment order by a second small
+ *   launch.  No atomics, seg_counters are not used, plan->xcd_order is ignored: results are run-to-run bit-identical.
+ *   A row without edges is written as zeros; view.nidx is not read.  The gathered rows take 32-bit offsets behind a
+ *   buffer descriptor when the table allows it and 64-bit addresses otherwise, as in stag_agg_fwd_w1.
+ * STAG_EINVAL: hidden <= 0; a row stride smaller than hidden; n_edges < 0 or >= 2^31; with n_edges > 0 a NULL
+ *   src / dst / ps / pd / h (forward) or own / other / g / d_own (backward); a csr that stag_agg_fwd refuses; a plan
+ *   without units, or with segments and no long_rows / long_seg_ptr / workspace.  STAG_ENOMEM: workspace too small.
+ *   STAG_ENOSYS (backward): a row stride of other or g of 2^32 bytes or more.  n_edges == 0 and n_dst == 0 return
+ *   STAG_OK; the backward still writes every row of d_own as zeros.  Every argument is checked before any device
+ *   work.                                                                                                          */
+int stag_edge_embed_fwd(const int32_t* src, const int32_t* dst, int64_t n_edges,
+                        const float* ps, int64_t ldps, const float* pd, int64_t ldpd, int32_t hidden,
+                        float* h, int64_t ldh, void* stream);
+int stag_edge_embed_bwd(const stag_csr* view, const stag_plan* plan,
+                        const float* own, int64_t ld_own, const float* other, int64_t ld_other, int32_t hidden,
+                        const float* g, int64_t ldg, float* d_own, int64_t ldd, void* stream);
+
 /* ---- sample-based KL against a mixture of Normals (stag/layers.py:141-143) ---------------------------------------
  * The reference's fallback when torch has no closed form for (q_a, p_a) — a MixtureSameFamily prior of Normals:
  *     q_a.log_prob(w).sum(-1).mean() - p_a.log_prob(w).sum(-1).mean()      on the forward's [E, Dn] sample w.

@@ -166,6 +166,9 @@ def bind(path):
     l.stag_edge_mlp_fwd.argtypes = [_vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]
     l.stag_edge_mlp_bwd.argtypes = [_vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int32, _vp, C.c_int32, _vp, _vp,
                                     _vp, _vp, _vp, C.c_size_t, _vp]
+    l.stag_edge_embed_fwd.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp, C.c_int64, _vp]
+    l.stag_edge_embed_bwd.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp,
+                                      C.c_int64, _vp, C.c_int64, _vp]
     l.stag_normal_kl_fwd.argtypes = [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     l.stag_normal_kl_bwd.argtypes = [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     l.stag_sample_kl_workspace_bytes.restype = C.c_size_t

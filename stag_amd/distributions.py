@@ -204,10 +204,15 @@ class AmortizedDistribution(Distribution):
             p_src = ops.node_linear(feat, lin.weight[:, :k].t())
             if shard:       # the source half travels: [n_rows, hidden] -> [n_buf, hidden]
                 p_src = graph.halo_gather(p_src)
-            h = (ops.gather_rows(graph, p_src, "src")
-                 + ops.gather_rows(graph, ops.node_linear(feat, lin.weight[:, k:].t(), lin.bias), "dst"))
-            for mod in list(self.embedding_mlp)[1:]:
-                h = mod(h)
+            p_dst = ops.node_linear(feat, lin.weight[:, k:].t(), lin.bias)
+            if not shard and ops.edge_embed_why_not(graph, p_src, p_dst, self.embedding_mlp) is None:
+                # Sequential(Linear, SiLU): both gathers, the add and the SiLU in one launch, and a backward that keeps
+                # no [E, hidden] pre-activation (ops.edge_embed, csrc/edge_embed.hip)
+                h = ops.edge_embed(graph, p_src, p_dst)
+            else:
+                h = ops.gather_rows(graph, p_src, "src") + ops.gather_rows(graph, p_dst, "dst")
+                for mod in list(self.embedding_mlp)[1:]:
+                    h = mod(h)
             heads = [self.parameters_mlp[n] for n in self.new_parameter_names]
             if sum(hd.out_features for hd in heads) <= 64:
                 # narrow heads ([E, 1] parameters): ONE product over the E rows of h, then split

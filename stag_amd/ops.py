@@ -688,6 +688,121 @@ def edge_mlp(graph, P, wh, bh=None):
     return _EdgeMlp.apply(graph, P, wh, bh)
 
 
+# ---- the wide edge embedding of amortised per-edge parameters (csrc/edge_embed.hip) ---------------------------------------
+# stag_edge_embed_fwd / _bwd | the composed route (two index_selects, an add and a SiLU over [E, hidden] tensors, the
+# pre-activation kept for SiLU's backward, two aggregations of explicit rows behind it).  The values agree within
+# tolerance either way: a speed and memory decision only.  True because no timed case is slower than the composed route
+# (profiles/r24/edge_embed.txt): the forward alone 59 against 148 us Cora-sized at hidden 1433, 107 against 368 us
+# Pubmed-sized at 500, 128 against 327 us on the PPI batch at 50, 258 against 1095 us at the arxiv shape at 128; forward +
+# backward 168 / 293 / 383 / 718 against 265 / 599 / 589 / 1727 us (two repeats of the composed route differ by 0.0-7.3 us,
+# of the fused one by 2.5-8.9); peak allocation of a forward + backward 73 / 207 / 157 / 572 against 188 / 545 / 447 /
+# 1545 MiB; a StagLayer(GCN, AmortizedDistribution(in, in), vi=True) training step 5.26 / 5.85 / 3.85 / 7.74 against 5.36 /
+# 6.19 / 4.08 / 8.79 ms.
+EDGE_EMBED_FUSED = True
+
+
+def edge_embed_why_not(graph, p_src, p_dst, mods):
+    """The first reason the wide branch of AmortizedDistribution.condition keeps the composed route, or None: the hidden
+    layer h = SiLU(p_src[src] + p_dst[dst]) comes from one stag_edge_embed_fwd launch and its gradients from two
+    stag_edge_embed_bwd launches.  mods: the modules of the embedding MLP.  One clause per case that has no fused form."""
+    if not EDGE_EMBED_FUSED:
+        return "switch"
+    if getattr(graph, "is_shard", False):
+        return "shard"
+    if not (getattr(p_src, "is_cuda", False) and getattr(p_dst, "is_cuda", False)) or not hasattr(graph, "_src"):
+        return "device"
+    if p_src.dim() != 2 or p_dst.dim() != 2 or p_src.shape != p_dst.shape or p_src.shape[1] == 0:
+        return "shape"
+    if any(t.dtype not in (torch.float32, torch.float16, torch.bfloat16) for t in (p_src, p_dst)):
+        return "dtype"
+    if torch.compiler.is_compiling():
+        return "compiling"
+    mods = list(mods)
+    if len(mods) != 2 or not isinstance(mods[0], torch.nn.Linear) or type(mods[1]) is not torch.nn.SiLU:
+        return "embedding"
+    return None
+
+
+def _rows32(t):
+    """t as fp32 rows with unit column stride: the tensor itself when it already is (any row stride the library takes —
+    the half of an [N, 2 hidden] table stays a view), else a packed copy."""
+    if (t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[1] <= t.stride(0) < _MAX_ROW_STRIDE
+            and t.shape[0] > 1):
+        return t
+    return _f32c(t)
+
+
+def _edge_embed_fwd_raw(src, dst, ps, pd, out=None):
+    """One stag_edge_embed_fwd: h [E, hidden] = SiLU(ps[src] + pd[dst]) on fp32 rows (_rows32), edges by edge id."""
+    dev = _lib.require_device(src, dst, ps, pd)
+    E, hidden = src.shape[0], ps.shape[1]
+    h = torch.empty((E, hidden), dtype=torch.float32, device=dev) if out is None else out
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_edge_embed_fwd(_lib.ptr(src), _lib.ptr(dst), E, _lib.ptr(ps), max(ps.stride(0), hidden),
+                                            _lib.ptr(pd), max(pd.stride(0), hidden), hidden, _lib.ptr(h),
+                                            max(h.stride(0), hidden), _lib.stream_of(dev))
+    _lib.check(rc, "stag_edge_embed_fwd")
+    return h
+
+
+def _edge_embed_bwd_raw(csrv, own, other, g, seg_len=DEFAULT_SEG_LEN, out=None):
+    """One stag_edge_embed_bwd on csrv: d_own [n_dst, hidden] from g [E, hidden] by edge id.  graph.csr with own = pd,
+    other = ps gives d pd; graph.csr_t with own = ps, other = pd gives d ps.  Plan order; bound through ctypes."""
+    dev = _lib.require_device(csrv.indptr, own, other, g)
+    hidden = own.shape[1]
+    if out is None:
+        out = torch.empty((csrv.n_dst, hidden), dtype=torch.float32, device=dev)
+    if csrv.n_dst == 0:
+        return out
+    plan_t = csrv.plan(seg_len)
+    nbytes = _lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], hidden, 0) if plan_t is not None else 0
+    plan_c, _keep = _plan_struct(csrv, seg_len, (hidden + 255) // 256, nbytes, dev, plan_t)
+    cs = csrv.struct()
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_edge_embed_bwd(
+            C.byref(cs), C.byref(plan_c) if plan_c is not None else None, _lib.ptr(own), max(own.stride(0), hidden),
+            _lib.ptr(other), max(other.stride(0), hidden), hidden, _lib.ptr(g), max(g.stride(0), hidden), _lib.ptr(out),
+            max(out.stride(0), hidden), _lib.stream_of(dev))
+    _lib.check(rc, "stag_edge_embed_bwd")
+    return out
+
+
+class _EdgeEmbed(torch.autograd.Function):
+    """h [E, hidden] = SiLU(p_src[src] + p_dst[dst]) by edge id: the hidden layer of an AmortizedDistribution with wide
+    heads on the two projected node tables (stag/distributions.py:178-183, 225-227), one launch forward
+    (stag_edge_embed_fwd).  Only the two [N, hidden] tables are saved: the backward forms the pre-activation again and
+    sums g * SiLU' over the in-edges of every destination and the out-edges of every source (stag_edge_embed_bwd on the
+    two CSR views), so nothing [E, hidden] is kept between the passes or allocated by the backward."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, p_src, p_dst, graph):
+        g = _owner(graph)
+        ps, pd = _rows32(p_src), _rows32(p_dst)
+        ctx.graph = g
+        ctx.save_for_backward(ps, pd)
+        return _edge_embed_fwd_raw(g._src, g._dst, ps, pd)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, gh):
+        ps, pd = ctx.saved_tensors
+        g = ctx.graph
+        gh = _rows32(gh)
+        d_src = _edge_embed_bwd_raw(g.csr_t, ps, pd, gh) if ctx.needs_input_grad[0] else None
+        d_dst = _edge_embed_bwd_raw(g.csr, pd, ps, gh) if ctx.needs_input_grad[1] else None
+        return d_src, d_dst, None
+
+
+def edge_embed(graph, p_src, p_dst):
+    """SiLU(p_src[u] + p_dst[v]) for every edge u -> v of graph, [E, hidden] by edge id, from the two projected node
+    tables [N, hidden] (unit column stride, any row stride).  edge_embed_why_not says when condition() takes it."""
+    n = graph.number_of_nodes()
+    if p_src.dim() != 2 or p_src.shape != p_dst.shape or p_src.shape[0] != n or p_src.shape[1] == 0:
+        raise ValueError(f"edge_embed: two [{n}, hidden] tables, got {tuple(p_src.shape)} and {tuple(p_dst.shape)}")
+    return _EdgeEmbed.apply(p_src, p_dst, graph)
+
+
 class _NormalKlMean(torch.autograd.Function):
     """mean over all elements of KL(N(loc, exp(log_scale)) || N(p_loc, p_scale)) with one-element prior parameters
     (torch.distributions.kl._kl_normal_normal; stag/layers.py:132-145): one pass forward, one backward, against
