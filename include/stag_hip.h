@@ -673,6 +673,44 @@ int stag_agg_bwd_w_mc(const stag_csr* csr, const stag_plan* plan, const float* x
                       const stag_noise_spec* spec, int32_t n_samples, int64_t offset_stride, int32_t reduce_k,
                       float* dw0, float* dw1, int64_t ldw, void* stream);
 
+/* ---- dx and both [E, D] parameter gradients of one draw from ONE pass over the source-major CSR (the backward of
+ * stag_agg_fwd with param_mode == STAG_PARAM_PER_EDGE: both layers of `citation_rec/gcn`), additive in v19 ----
+ * On csr_t rows are source nodes u, indices are destination rows v, nidx is the forward CSR position (the draw) and eid
+ * the edge id (the parameter and gradient rows).  The row of x an edge's gradients need is the unit's own row there, the
+ * row of g is the one the dx pass gathers anyway:
+ *   dx[u, k]       = row_scale[u] * sum_{p in row u} w[p, k] * (g_scale[v_p] * g[v_p, k])
+ *   val[p, k]      = (row_scale[u] * x[u, k]) * (g_scale[v_p] * g[v_p, k])                      (NULL scale: factor left out)
+ *   dp_i[eid_p, k] = D_i[p, k] * val[p, k]                                                      i = 0, 1
+ * w, D_0 and D_1 come from ONE Philox block per edge and chunk: exactly what stag_agg_bwd_w writes to dw and dw1 for that
+ * spec when dw1 != NULL (with spec.p1_log, D_1 is the derivative with respect to the log-scale); relu, p1_log, pos_base
+ * and epoch are honoured as there.  dx may be NULL (parameter gradients only); dp1 may be NULL; dp0 is required.  dp0 and
+ * dp1 are [E, D] by edge id, rows ldp floats apart; p0 and p1 rows D floats apart, as stag_agg_fwd takes them.
+ *   Per edge, the destination id, the edge id, the position, the lane's 4 values of p0[e, :] and p1[e, :] (exponentiated
+ *   there, once, when spec.p1_log) and the lane's 4 channels of g[v] are read ONCE; x[u] and row_scale[u] are the unit's
+ *   own and are loaded once per unit.  The two gradient rows of an edge are stored where the edge is walked: products
+ *   only, no merge.  The dx sums follow the plan-order rule of stag_agg_fwd_mc_pedge above (blocks of 4 consecutive
+ *   positions that start at +0, folded in order, Kahan-compensated in long units; a long source row's segments leave their
+ *   partials in plan_t->workspace, >= stag_plan_workspace_bytes(n_seg, D, 0) bytes, and a second small launch adds them in
+ *   segment order and applies row_scale): no atomics, no arrival counters, results are run-to-run bit-identical.
+ *   dx is stag_agg_fwd_mc_pedge(csr_t, x = g, n_samples = 1, SUM, src_scale = g_scale, dst_scale = row_scale) bit for bit;
+ *   dp0 / dp1 are stag_agg_bwd_w_mc(csr, n_samples = 1, reduce_k = 0, src_scale = row_scale, the same g_scale) bit for
+ *   bit, and do not depend on the plan.  Rows without out-edges get zeros in dx.  seg_counters are not used;
+ *   plan_t->xcd_order is ignored (plan order).  Any D >= 1: D % 4 != 0, an unaligned pointer or an unaligned stride take
+ *   the scalar row forms, with the same bits; channels past 256 go to further channel tiles.  Without dx the workspace
+ *   is not needed.
+ *   STAG_EINVAL: a NULL csr_t / g / spec / x / dp0; a NULL p0 / p1, csr_t->eid or csr_t->nidx of a graph with edges (the
+ *   per-edge arrays of a graph without edges have no address); D <= 0; ldg < D; 0 < ldx < D; dx with ldo < D; ldp < D; kind
+ *   NONE / EXPLICIT / BERNOULLI; a param_mode other than PER_EDGE (PER_EDGE1 is stag_agg_bwd_edge's, SCALAR / PER_CHANNEL
+ *   are stag_agg_bwd_dp's); deriv != 0; the counter bounds of stag_agg_fwd; a plan without units.  STAG_ENOSYS — the
+ *   caller keeps stag_agg_bwd + stag_agg_bwd_w: in_norm; ldx == 0 (a broadcast row); chunk_base != 0; a launch across a
+ *   2^32 boundary of the global position; ldg * 4 or ldx * 4 >= 2^32.  STAG_ENOMEM: workspace too small.  STAG_EINVAL
+ *   comes before STAG_ENOSYS, that before STAG_ENOMEM.  Every argument is checked before any device work; a graph without
+ *   rows or without edges returns STAG_OK after the checks, with dx zeroed where it has rows.                          */
+int stag_agg_bwd_pedge(const stag_csr* csr_t, const stag_plan* plan_t, const float* g, int64_t ldg, int32_t D,
+                       const stag_noise_spec* spec, const float* g_scale, const float* row_scale,
+                       const float* x, int64_t ldx, float* dx, int64_t ldo,
+                       float* dp0, float* dp1, int64_t ldp, void* stream);
+
 /* per-graph readout of a batched graph: out[b,:] = sum|mean of x[offsets[b]:offsets[b+1],:]
  * (dgl.sum_nodes / dgl.mean_nodes, stag/layers.py:165,177)                      */
 int stag_segment_reduce(const float* x, int64_t ldx, int32_t D,

@@ -240,6 +240,8 @@ def bind(path):
     l.stag_agg_bwd_w_mc.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int32,
                                     _vp, _vp, C.POINTER(NoiseSpec), C.c_int32, C.c_int64, C.c_int32, _vp, _vp, C.c_int64,
                                     _vp]
+    l.stag_agg_bwd_pedge.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, C.c_int64, C.c_int32, C.POINTER(NoiseSpec),
+                                     _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp]
     l.stag_reorder_workspace_bytes.restype = C.c_size_t
     l.stag_reorder_workspace_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]
     l.stag_reorder_locality.argtypes = [C.POINTER(Csr), C.POINTER(Csr), C.c_int32, C.c_int32, C.c_uint64, _vp, _vp, _vp,

@@ -308,6 +308,28 @@ def _agg_bwd_edge_raw(csrv_t, g, x, D, spec, g_scale, row_scale, seg_len, want_d
     return dx, e0, e1
 
 
+def _agg_bwd_pedge_raw(csrv_t, g, x, D, spec, g_scale, row_scale, seg_len, want_dx=True, want_p1=True):
+    """One stag_agg_bwd_pedge launch on the source-major CSR: dx (if wanted) and the gradients of the [E, D] parameter
+    tables, by edge id (the second only if wanted).  Bound through ctypes only; the plan is walked in plan order."""
+    dev = _lib.require_device(g, x, csrv_t.indptr, g_scale, row_scale)
+    dx = torch.empty((csrv_t.n_dst, D), dtype=torch.float32, device=dev) if want_dx else None
+    e0 = torch.empty((csrv_t.n_edges, D), dtype=torch.float32, device=dev)
+    e1 = torch.empty_like(e0) if want_p1 else None
+    if csrv_t.n_edges == 0 or csrv_t.n_dst == 0:        # (an empty table has no address to hand over)
+        return (dx.zero_() if want_dx else None), e0, e1
+    plan_t = csrv_t.plan(seg_len)
+    nbytes = _lib.lib().stag_plan_workspace_bytes(plan_t["n_seg"], D, 0) if plan_t is not None and want_dx else 0
+    plan_c, _keep = _plan_struct(csrv_t, seg_len, (D + 255) // 256, nbytes, dev, plan_t=plan_t)
+    cs = csrv_t.struct()
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_agg_bwd_pedge(
+            C.byref(cs), C.byref(plan_c) if plan_c is not None else None, _lib.ptr(g), g.stride(0), D,
+            C.byref(spec), _lib.ptr(g_scale), _lib.ptr(row_scale), _lib.ptr(x), x.stride(0),
+            _lib.ptr(dx), D, _lib.ptr(e0), _lib.ptr(e1), D, _lib.stream_of(dev))
+    _lib.check(rc, "stag_agg_bwd_pedge")
+    return dx, e0, e1
+
+
 def _agg_bwd_dp_raw(csrv_t, g, x, D, spec, g_scale, row_scale, seg_len, want_dx=True):
     """One stag_agg_bwd_dp launch on the source-major CSR: dx (if wanted) and the FINISHED gradients of scalar /
     per-channel parameters, dp0 [D], dp1 [D] (x = None: ones in its place)."""
@@ -1226,6 +1248,14 @@ class _AggregateVI(torch.autograd.Function):
             # row of x an edge's gradient needs is the unit's own row there
             dx, e0, e1 = _agg_bwd_edge_raw(graph.csr_t, g, x, D, spec_c, dvec, src_scale, ctx.seg_len,
                                            want_dx=ctx.needs_input_grad[0])
+            rows = {1: e0, 2: e1}
+            need_p = False
+        elif (need_p and q is None and noise.param_mode == _lib.PARAM_PER_EDGE
+              and pedge_bwd_why_not(x, noise, graph, ctx.needs_input_grad[0]) is None):
+            # [E, D] (amortised) parameters: dx and both gradient tables from ONE transposed pass (stag_agg_bwd_pedge);
+            # dvec rides along as g_scale, so no [N, D] product is formed
+            dx, e0, e1 = _agg_bwd_pedge_raw(graph.csr_t, g, x, D, spec_c, dvec, src_scale, ctx.seg_len,
+                                            want_p1=ctx.needs_input_grad[2])
             rows = {1: e0, 2: e1}
             need_p = False
         elif ctx.needs_input_grad[0]:
@@ -2180,11 +2210,21 @@ class _AggregateMCPEdge(torch.autograd.Function):
         if fused:
             d0, d1 = _bwd_w_mc_raw(graph.csr, x, g_all, D, src_scale, dvec, _targs_or_c(_noise_spec(ctx.noise, in_norm=0)),
                                    ctx.S, ctx.stride, reduce_k=False, seg_len=ctx.seg_len)
+        # a sample's dx and both of its [E, D] gradients from one transposed pass (stag_agg_bwd_pedge), where x needs a
+        # gradient and the batched call above did not take the parameters
+        one_pass = (PEDGE_BWD_MC_LOOP and need_x and need_p and not fused
+                    and pedge_bwd_why_not(x, ctx.noise, graph, need_x) is None)
         for s_i in range(ctx.S if (need_x or not fused) else 0):
             nz = copy.copy(ctx.noise)
             nz.offset = (ctx.noise.offset + s_i * ctx.stride) & _MASK64
             spec = _noise_spec(nz, in_norm=0)
             g = g_all[s_i]
+            if one_pass:
+                dxs, e0, e1 = _agg_bwd_pedge_raw(graph.csr_t, g, x, D, _targs_or_c(spec), dvec, src_scale, ctx.seg_len)
+                dx = dxs if dx is None else dx.add_(dxs)
+                d0 = e0 if d0 is None else d0.add_(e0)
+                d1 = e1 if d1 is None else d1.add_(e1)
+                continue
             if need_x:
                 dxs, _, _ = _agg_bwd_raw(graph.csr_t, g, D, spec, dvec, src_scale, ctx.seg_len, False)
                 dx = dxs if dx is None else dx.add_(dxs)
@@ -2200,6 +2240,71 @@ class _AggregateMCPEdge(torch.autograd.Function):
                     shape = ctx.pshapes[i]
                     dp[i] = d.sum_to_size(shape) if d.dim() >= len(shape) and shape != d.shape else d.reshape(shape)
         return dx, dp[0], dp[1], None, None, None, None, None, None, None, None
+
+
+# ---- dx and both [E, D] parameter gradients of one draw from ONE transposed pass --------------------------------------
+# stag_agg_bwd_pedge: on the source-major CSR the row of x an edge's gradients need is the unit's own row and the row of g
+# is the one the dx pass gathers anyway, so one walk (one gather, one read of each parameter table, one Philox block per
+# edge and chunk) replaces stag_agg_bwd on csr_t + the [N, D] product g * dvec + stag_agg_bwd_w on csr, which gathers a row
+# per edge again, reads both tables again and draws the same blocks again.  Taken by _AggregateVI.backward, and by the
+# per-sample loop of _AggregateMCPEdge.backward (PEDGE_BWD_MC_LOOP), for [E, D] parameters without in-norm when x needs a
+# gradient as well; without dx stag_agg_bwd_w alone is already one pass.
+# Compiler's report (csrc/_obj/agg_bwd_pedge.remarks): 0 bytes of scratch in all 15 instantiations; the walk takes 129 VGPRs
+# for Normal (3 waves per SIMD) and 122 for Uniform (4), the merge 92-96 (5).
+# Measured (profiles/r25/pedge_bwd.txt; us per backward call, one pass / the three launches, Normal + log-scale | Uniform;
+# two repeats of the three launches differ by 0.6-12.3, of the one pass by 0.0-6.2):
+#   arxiv D = 128          676 /  943 | 535 /  925        PPI batch D = 50      350 / 489 | 373 / 521
+#   PPI batch D = 256      852 / 1172 | 669 / 1138        Pubmed-sized D = 500  237 / 443 | 224 / 457
+#   Cora-sized D = 1433    121 /  663 | 118 /  660        Cora-sized D = 16      19 / 102 |  19 / 102
+# The training step of StagLayer(GCN(in, in), AmortizedDistribution(in, in), vi=True) on an input that needs a gradient, ms,
+# switch on / off: 8.15 / 8.39, 4.12 / 4.23, 13.19 / 13.48, 5.41 / 5.64, 5.02 / 5.60, 1.93 / 1.93 (in that order).
+# The switch ships True by the usual rule (True only if the one pass is not slower than the three launches, beyond the
+# spread of two repeats, for EVERY case timed): all 18 cases meet it.
+PEDGE_BWD_FUSED = True
+# ... and whether the per-sample loop of _AggregateMCPEdge.backward takes it as well.  Ships False: that loop was not among
+# the cases timed (the rule asks for a measurement of every case a switch turns on), and tests/test_gpu_mc_bwd.py holds the
+# loop at the shipped defaults to one stag_agg_bwd_w call per sample.  tests/test_gpu_bwd_pedge.py runs it switched on.
+PEDGE_BWD_MC_LOOP = False
+
+
+def pedge_bwd_why_not(x, noise, graph, need_x):
+    """The first reason the backward of an aggregation with [E, D] noise parameters (_AggregateVI, the per-sample loop of
+    _AggregateMCPEdge) does not take dx and both gradient tables from one stag_agg_bwd_pedge call, or None.  One clause per
+    refusal of the entry point (include/stag_hip.h) and per path without a form there; whatever gets a reason keeps
+    stag_agg_bwd + stag_agg_bwd_w.  need_x: x needs a gradient — without it stag_agg_bwd_w alone is one pass already."""
+    if not PEDGE_BWD_FUSED:
+        return "switch"
+    if x.dim() != 2:
+        return "shape"
+    if x.stride(0) == 0:
+        return "broadcast row"
+    if x.dtype != torch.float32:
+        return "dtype"
+    if not isinstance(noise, EdgeNoise):
+        return "no descriptor"
+    if noise.param_mode != _lib.PARAM_PER_EDGE:
+        return "noise parameters"
+    if noise.dn != x.shape[1]:
+        return "noise width"
+    if noise.in_norm:
+        return "in-norm"
+    if noise.kind not in (_lib.NOISE_NORMAL, _lib.NOISE_UNIFORM):
+        return "kind"
+    if noise.deriv:
+        return "derivative selector"
+    if noise.chunk_base:
+        return "channel shard"
+    if (noise.pos_base & 0xFFFFFFFF) + noise.graph.number_of_edges() > (1 << 32):
+        return "position range"
+    if getattr(graph, "is_shard", False) or getattr(noise.graph, "is_shard", False):
+        return "shard"
+    if not need_x:
+        return "no dx"
+    if torch.compiler.is_compiling():
+        return "compiling"
+    if not x.is_cuda:
+        return "device"
+    return None
 
 
 # ---- The per-edge parameter gradients of a Monte-Carlo batch from one pass ---------------------------------------------
