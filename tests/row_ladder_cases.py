@@ -514,3 +514,62 @@ def gat_f32(g, el, er, ft, slope, W=None):
         attn[g.eid[p]] = a
         out[v] = (a[:, :, None] * ft[u]).sum(0, dtype=f)
     return out, attn
+
+
+# ---- the wide edge embedding: stag_edge_embed_bwd over the ladder, stag_edge_embed_fwd over its tails -----------------------
+EMBED_WIDTHS = (3, 16, 64, 256, 260)
+EMBED_OWN, EMBED_OTHER = (0.0, 64.0), (0.0, 64.0, -256.0)
+EMBED_CLASS = {0.0: (0.0, 0.5), 64.0: (64.0, 1.0), 128.0: (128.0, 1.0), -256.0: (-0.0, 0.0), -192.0: (-0.0, 0.0)}   # pre: (SiLU, SiLU')
+EMBED_ORIENT = {"d pd": ("f", "rows"), "d ps": ("s", "src")}      # the view each orientation walks, and what its rows are
+EMBED_FWD_WIDTHS = {16: 4, 256: 64, 5: 4, 260: 64}                # hidden: lanes per edge (T = 256 / lanes teams per block)
+EMBED_FWD_NODES = 37
+
+
+def embed_view(st, orient):
+    return st.ogf if EMBED_ORIENT[orient][0] == "f" else st.ogs
+
+
+def embed_tables(hidden, exact, orient):
+    """own [N, hidden] (the rows the units own: pd for d pd, ps for d ps), other [N, hidden] (the gathered table), g [E, hidden]
+    by edge id.  exact: own in {0, 64}, other in {0, 64, -256} (one in five: most terms count), g nonzero integers in [-8, 8]."""
+    key = ("embed", hidden, exact, orient)
+    if key not in _CACHE:
+        rng = np.random.default_rng((9000 if exact else 8000) + hidden + (500 if orient == "d ps" else 0))
+        f = np.float32
+        if exact:
+            own = rng.choice(EMBED_OWN, (N, hidden)).astype(f)
+            other = rng.choice(EMBED_OTHER, (N, hidden), p=(0.4, 0.4, 0.2)).astype(f)
+            g = (rng.integers(1, 9, (N_EDGES, hidden)) * rng.choice([-1, 1], (N_EDGES, hidden))).astype(f)
+        else:
+            own, other = rng.standard_normal((N, hidden)).astype(f), rng.standard_normal((N, hidden)).astype(f)
+            g = rng.standard_normal((N_EDGES, hidden)).astype(f)
+        _CACHE[key] = (own, other, g)
+    return _CACHE[key]
+
+
+def embed_bwd_reference(view, own, other, g, exact=False):
+    """(d_own [rows, hidden], sum |terms|) in float64: sum over a row's positions of g[eid] SiLU'(own[row] + other[column]),
+    the pre-activation rounded to fp32 first.  exact: float64 SiLU' rounded to fp32 (the class table: SiLU'(-256) is -1e-109
+    before that rounding), so that the sums are those of fp32 numbers."""
+    import edge_embed_range_cases as ec
+    rows = view.dst_of_pos
+    pre = (own[rows] + other[view.indices]).astype(np.float32)
+    dh = ec.silu64(pre.astype(np.float64))[1]
+    term = g[view.eid].astype(np.float64) * (dh.astype(np.float32).astype(np.float64) if exact else dh)
+    out, ab = np.zeros((view.n_dst, own.shape[1])), np.zeros((view.n_dst, own.shape[1]))
+    np.add.at(out, rows, term)
+    np.add.at(ab, rows, np.abs(term))
+    return out, ab
+
+
+def embed_fwd_sizes(lanes):
+    T = 256 // lanes
+    return sorted({1, T - 1, T, T + 1, 4 * T - 1, 4 * T, 4 * T + 1})
+
+
+def embed_fwd_case(hidden, E):
+    """src, dst [E] int32 over EMBED_FWD_NODES nodes, ps in {0, 64}, pd in {0, 64, -256}: SiLU is exact in fp32"""
+    rng = np.random.default_rng(100 * hidden + E)
+    f, n = np.float32, EMBED_FWD_NODES
+    return (rng.integers(0, n, E).astype(np.int32), rng.integers(0, n, E).astype(np.int32),
+            rng.choice(EMBED_OWN, (n, hidden)).astype(f), rng.choice(EMBED_OTHER, (n, hidden)).astype(f))

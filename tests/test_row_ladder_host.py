@@ -5,7 +5,8 @@ segments); the unit batches of the cooperative GAT kernels close on the unit cap
 an empty unit; the exact cases are exact (every sum of |terms| is a multiple of 1/4 below 2^22) and the oracle agrees with
 a float64 numpy loop on them bit for bit; and the float64 oracle and a float32 restatement of every TOL case lie within
 util.TOL of each other (STAG_PRINT_ERR=1 prints each distance), so the plain bar is the right one for rows of at most 132
-terms."""
+terms.  For the wide edge embedding: SiLU and SiLU' are exact at the five pre-activations of its exact case, its sums are
+multiples of 1/2 below 2^22, and a float32 restatement of its N(0, 1) case meets util.assert_close_cond's bar."""
 import numpy as np
 import pytest
 
@@ -115,6 +116,73 @@ def test_the_oracle_against_a_float32_restatement(oracle, st, D, half):
     one = rl.bwd_w_reference(oracle, st, T, 1, rl.MCB_STRIDE, None)
     for r in refs + one:
         assert r.shape == (rl.N_EDGES, D) and np.isfinite(r).all() and np.abs(r).max() > 0
+
+
+def test_the_edge_embedding_s_classes_are_exact():
+    """The five pre-activations of the exact edge-embedding case: float64 SiLU and SiLU' rounded to fp32 are the class table
+    (so is the documented formula in numpy float32), and the table is what own + other can give."""
+    import edge_embed_range_cases as ec
+    f = np.float32
+    sums = {float(f(a) + f(b)) for a in rl.EMBED_OWN for b in rl.EMBED_OTHER}
+    assert sums == set(rl.EMBED_CLASS) and len(sums) == 5
+    for pre, (h, dh) in rl.EMBED_CLASS.items():
+        h64, d64 = ec.silu64(np.float64(pre))
+        assert f(h64) == f(h) and f(d64) == f(dh), (pre, h64, d64)
+        h32, d32 = ec.silu32(f(pre))
+        assert h32 == f(h) and d32 == f(dh), (pre, h32, d32)
+    assert sorted(v[1] for v in rl.EMBED_CLASS.values()) == [0.0, 0.0, 0.5, 1.0, 1.0]
+
+
+@pytest.mark.parametrize("orient", list(rl.EMBED_ORIENT))
+@pytest.mark.parametrize("hidden", rl.EMBED_WIDTHS)
+def test_the_edge_embedding_s_exact_case_is_exact(st, hidden, orient):
+    """Every term g SiLU' is a multiple of 1/2, sum |terms| of every row stays below 2^22: any order of fp32 additions,
+    compensated or not, gives the float64 sum.  Every edge counts in some channel, so a dropped edge changes its row."""
+    view = rl.embed_view(st, orient)
+    own, other, g = rl.embed_tables(hidden, True, orient)
+    assert set(np.unique(own)) <= set(rl.EMBED_OWN) and set(np.unique(other)) <= set(rl.EMBED_OTHER)
+    assert np.array_equal(g, np.round(g)) and np.abs(g).max() <= 8 and np.abs(g).min() >= 1
+    ref, ab = rl.embed_bwd_reference(view, own, other, g, exact=True)
+    assert ab.max() < 2.0 ** 22 and 132 * 8 < 2.0 ** 22
+    assert np.array_equal(ref * 2, np.round(ref * 2)) and np.array_equal(ref, ref.astype(np.float32).astype(np.float64))
+    # the reference again from the class table
+    pre = own[view.dst_of_pos] + other[view.indices]
+    dh = np.vectorize(lambda v: rl.EMBED_CLASS[float(v)][1])(pre)
+    again = np.zeros_like(ref)
+    np.add.at(again, view.dst_of_pos, g[view.eid].astype(np.float64) * dh)
+    assert np.array_equal(again, ref)
+    counts = (dh != 0).sum(1)
+    assert (counts > 0).mean() > (0.9 if hidden == 3 else 0.999), "an edge's term is nonzero in some channel"
+    assert ref.shape == (rl.N, hidden) and (ref[np.diff(view.indptr) == 0] == 0).all()
+
+
+@pytest.mark.parametrize("orient", list(rl.EMBED_ORIENT))
+@pytest.mark.parametrize("hidden", rl.EMBED_WIDTHS)
+def test_the_edge_embedding_s_tol_case_against_a_float32_restatement(st, hidden, orient):
+    """N(0, 1) tables: the formula in float32, terms added in position order without compensation, within
+    util.assert_close_cond's bar of the float64 reference (the plain distance is printed under STAG_PRINT_ERR=1)."""
+    import edge_embed_range_cases as ec
+    from util import assert_close_cond
+    view = rl.embed_view(st, orient)
+    own, other, g = rl.embed_tables(hidden, False, orient)
+    ref, ab = rl.embed_bwd_reference(view, own, other, g)
+    term = g[view.eid] * ec.silu32(own[view.dst_of_pos] + other[view.indices])[1]
+    got = np.zeros((rl.N, hidden), np.float32)
+    for p in range(view.n_edges):
+        got[view.dst_of_pos[p]] += term[p]
+    assert_close_cond(got, ref, ab, what=f"float32 restatement {orient} hidden={hidden}")
+
+
+def test_the_edge_embedding_s_forward_tails():
+    for hidden, lanes in rl.EMBED_FWD_WIDTHS.items():
+        nchunk = (hidden + 3) // 4
+        assert min(64, max(4, 1 << (nchunk - 1).bit_length())) == lanes, "lanes_for(nchunk, 4) of csrc/entry_args.hpp"
+        T = 256 // lanes
+        sizes = rl.embed_fwd_sizes(lanes)
+        assert {T - 1, T, T + 1, 4 * T - 1, 4 * T, 4 * T + 1, 1} == set(sizes) and sizes[-1] == 4 * T + 1
+        src, dst, ps, pd = rl.embed_fwd_case(hidden, sizes[-1])
+        pre = ps[src] + pd[dst]
+        assert set(np.unique(pre).tolist()) <= set(rl.EMBED_CLASS) and len(np.unique(pre)) == 5
 
 
 @pytest.mark.parametrize("H,F", rl.GAT_SHAPES)
