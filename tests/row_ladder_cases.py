@@ -472,6 +472,50 @@ def bwd_w_reference(O, st, T, n_samples, stride, gs):
     return refs
 
 
+# ---- stag_agg_bwd_pedge over the source-major view (the out-degree ladder and, at seg_len 4, its cut rows) ---------------------
+PEDGE_WIDTHS = (3, 16, 64, 260)
+
+
+def pedge_specs(D):
+    """(exact, tol): Normal(integer loc, 0) — w == loc and d/dloc == 1 exactly — on the exact tables; Normal [E, D] tables
+    with log-scales on the N(0, 1) tables"""
+    Te, Tt = tables(D, True), tables(D, False)
+    return (Spec("normal", Te.w, np.zeros_like(Te.w)),
+            Spec("normal", Tt.q0, np.log(Tt.q1).astype(np.float32), p1_log=True))
+
+
+def pedge_reference(O, st, T, spec, f32=False):
+    """(dx [N, D] over the sources, dp0, dp1 [E, D] by edge id, sum |terms| of dx) in float64.  On ogs rows are sources u, the
+    columns destinations v, nidx the positions of ogf (the draw), eid the edge ids: T.own holds the rows the units own
+    (row_scale = T.ds), T.x the gathered table (g_scale = T.ss):
+        dx[u] = ds[u] sum_p w[p] (ss[v] x[v]),  dp_i[eid_p] = D_i[p] (ds[u] own[u]) (ss[v] x[v]).
+    f32: dx again with every term rounded to fp32 and added in edge order."""
+    s, D = st.ogs, T.D
+    rows, cols, eid = s.dst_of_pos, s.indices, s.eid
+    case = Case("weights", "fwd", spec, view="f")
+    W, D1, D2 = (weights(O, st, case, D, deriv=d) for d in (0, 1, 2))
+    ft = np.float32 if f32 else np.float64
+    gg = (T.ss[cols, None].astype(ft) * T.x[cols].astype(ft)).astype(ft)
+    xx = (T.ds[rows, None].astype(ft) * T.own[rows].astype(ft)).astype(ft)
+    dx, ab = np.zeros((N, D), ft), np.zeros((N, D), np.float64)
+    for p in range(N_EDGES):                                   # in edge order
+        dx[rows[p]] = dx[rows[p]] + (W[eid[p]].astype(ft) * gg[p]).astype(ft)
+        ab[rows[p]] += np.abs(W[eid[p]].astype(np.float64) * gg[p])
+    dx = (dx * T.ds[:, None].astype(ft)).astype(ft)
+    ab *= T.ds[:, None]
+    val = (xx * gg).astype(ft)
+    dp0, dp1 = np.zeros((N_EDGES, D), ft), np.zeros((N_EDGES, D), ft)
+    dp0[eid], dp1[eid] = (D1[eid].astype(ft) * val).astype(ft), (D2[eid].astype(ft) * val).astype(ft)
+    return dx, dp0, dp1, ab
+
+
+def source_row_class(st, seg_len):
+    """per source row of ogs: 2 = cut into segments (long), 1 = a whole-row unit of more than 16 edges (Kahan), 0 = plain"""
+    deg = st.outdeg
+    long_row = (deg > seg_len) if seg_len else np.zeros(N, bool)
+    return np.where(long_row, 2, np.where(deg > HEAVY_LEN, 1, 0))
+
+
 # ---- GAT ---------------------------------------------------------------------------------------------------------------------
 def gat_inputs(H, F):
     """el, er [N, H], ft, G [N, H, F] N(0, 1), w [E, H] explicit weights by edge id"""

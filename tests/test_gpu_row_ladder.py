@@ -18,7 +18,10 @@ STAG_AGG_PLAIN=0, STAG_COMBINE_GROUPS=0 against the default, a Monte-Carlo sampl
 stag_agg_bwd_w_mc at S = 1 against stag_agg_bwd_w, stag_gat_fwd_half against stag_gat_fwd on the widened rows.
 tests/test_row_ladder_host.py proves the fixture, the plans, the batches and the references without a GPU.  The wide edge
 embedding (stag_edge_embed_bwd over the ladder in both orientations, stag_edge_embed_fwd over the tails of its edge grid) is
-at the end of the file, with exact values of its own: SiLU and SiLU' are exact at the five pre-activations it uses."""
+follows, with exact values of its own: SiLU and SiLU' are exact at the five pre-activations it uses.  Last,
+stag_agg_bwd_pedge over the source-major view (the out-degrees 0..21; cut rows at seg_len 4): exact on integers and
+Normal(integer loc, 0) tables, at util.TOL on Normal [E, D] tables with log-scales, and bit for bit against
+stag_agg_bwd_w_mc and stag_agg_fwd_mc_pedge at one sample."""
 import numpy as np
 import pytest
 import torch
@@ -612,3 +615,50 @@ def test_edge_embed_forward_tails(dev, hidden):
         if not np.isnan(got[E:]).all():
             bad.append(f"hidden={hidden} E={E}: rows behind the last edge were written")
     assert not bad, "\n".join(bad)
+
+
+# ---- stag_agg_bwd_pedge over the source-major view: the out-degree ladder 0..20 and, at seg_len 4, its cut rows -----------
+@pytest.mark.parametrize("D", rl.PEDGE_WIDTHS)
+def test_bwd_pedge_over_the_out_degree_ladder(dev, oracle, D):
+    """dx (a sum over a source's out-edges, in plan order) and the two [E, D] gradient tables (products stored where the edge
+    is walked) for every out-degree, without a plan, at seg_len 64 (whole rows, Kahan past 16) and 4 (rows of more than 4
+    edges cut).  EXACT: integers and Normal(integer loc, 0) — dx equals the integer sums and dp0 the integer products bit
+    for bit.  AT util.TOL: Normal [E, D] tables with log-scales against the float64 restatement, and bit for bit against
+    the entries whose arithmetic it restates: stag_agg_bwd_w_mc at one sample on the forward view (dp0, dp1) and
+    stag_agg_fwd_mc_pedge at one sample on this view (dx).  Leaving dx or dp1 out changes no other output."""
+    from stag_amd import _lib, ops
+    rig = _rig(oracle, dev)
+    st, errs = rig.st, _Errs(rig.st)
+    V, F = rig.views["s"], rig.views["f"]
+    ran = 0
+    with hw_normals(oracle, dev):
+        for exact, spec in zip((True, False), rl.pedge_specs(D)):
+            T, t = rl.tables(D, exact), rig.tables(D, exact)
+            rdx, rd0, rd1, _ = rl.pedge_reference(oracle, st, T, spec)
+            sp = spec.c(dev)
+            for seg in rl.SEGS:
+                what = f"stag_agg_bwd_pedge D={D} {'exact' if exact else 'Normal p1_log'} seg_len={seg}"
+                dx, d0, d1 = (_np(o) for o in ops._agg_bwd_pedge_raw(V, t["x"], t["own"], D, sp, t["ss"], t["ds"], seg))
+                if exact:
+                    errs.exact(dx, rdx, "src", f"{what} dx")
+                    errs.exact(d0, rd0, "edge", f"{what} dp0")
+                else:
+                    errs.close(dx, rdx, "src", f"{what} dx")
+                    errs.close(d0, rd0, "edge", f"{what} dp0", scaled=True)
+                    errs.close(d1, rd1, "edge", f"{what} dp1", scaled=True)
+                w0, w1 = ops._bwd_w_mc_raw(F, t["own"], t["x"][None].contiguous(), D, t["ds"], t["ss"], sp, 1, 1, seg_len=seg)
+                errs.same_bits(d0, _np(w0), "edge", f"{what} dp0 vs stag_agg_bwd_w_mc at one sample")
+                errs.same_bits(d1, _np(w1), "edge", f"{what} dp1 vs stag_agg_bwd_w_mc at one sample")
+                mc = ops._agg_fwd_mc_pedge_raw(V, t["x"], _Noise(sp), 1, 1, _lib.REDUCE_SUM, t["ss"], t["ds"], seg)
+                errs.same_bits(dx, _np(mc[0]), "src", f"{what} dx vs stag_agg_fwd_mc_pedge at one sample")
+                n0, e0, e1 = ops._agg_bwd_pedge_raw(V, t["x"], t["own"], D, sp, t["ss"], t["ds"], seg, want_dx=False)
+                assert n0 is None
+                errs.same_bits(_np(e0), d0, "edge", f"{what} dp0 without dx")
+                errs.same_bits(_np(e1), d1, "edge", f"{what} dp1 without dx")
+                x2, e0, n1 = ops._agg_bwd_pedge_raw(V, t["x"], t["own"], D, sp, t["ss"], t["ds"], seg, want_p1=False)
+                assert n1 is None
+                errs.same_bits(_np(x2), dx, "src", f"{what} dx without dp1")
+                errs.same_bits(_np(e0), d0, "edge", f"{what} dp0 without dp1")
+                ran += 1
+    assert ran == 2 * len(rl.SEGS)
+    errs.done()

@@ -202,3 +202,51 @@ def test_the_gat_oracle_against_a_float32_restatement(oracle, st, H, F):
         sums = np.zeros((rl.N, H))
         np.add.at(sums, st.row_of_pos, attn[st.ogf.eid].astype(np.float64))
         assert scaled_err(sums[st.indeg > 0], 1.0) <= TOL and (sums[st.indeg == 0] == 0).all()
+
+
+# ---- stag_agg_bwd_pedge over the source-major view -------------------------------------------------------------------------
+def test_bwd_pedge_source_rows(st):
+    """The out-degrees carry 0..20 once each and more than 16 elsewhere: without a plan and at seg_len 64 no source row is
+    cut, rows of up to 16 edges are plain sums and the longer ones Kahan units; at seg_len 4 every row of more than 4 edges
+    is cut, up to 6 segments, and the rows of 0..4 stay whole."""
+    s = st.ogs
+    assert np.array_equal(np.diff(s.indptr), st.outdeg) and sorted(s.nidx) == list(range(rl.N_EDGES))
+    assert np.array_equal(st.ogf.eid[s.nidx], s.eid), "nidx: the position of the same edge in the forward view"
+    assert set(rl.OUT_LADDER) <= set(st.outdeg.tolist()) and st.outdeg.max() <= 64
+    for seg, classes in ((0, {0, 1}), (64, {0, 1}), (4, {0, 2})):
+        cls = rl.source_row_class(st, seg)
+        assert set(cls.tolist()) == classes
+        if seg:
+            p = rl.host_plan(s.indptr, seg)
+            assert p["n_long"] == (cls == 2).sum() and p["n_heavy"] - p["n_seg"] == (cls == 1).sum()
+    p4 = rl.host_plan(s.indptr, 4)
+    assert max(p4["segs"].values()) == -(-int(st.outdeg.max()) // 4) and min(p4["segs"].values()) == 2
+    assert {int(d) for d in st.outdeg[rl.source_row_class(st, 4) == 0]} == {0, 1, 2, 3, 4}
+    assert (rl.source_row_class(st, 64) == 1).sum() >= 10 and (st.outdeg == 17).any() and (st.outdeg == 16).any()
+
+
+@pytest.mark.parametrize("D", rl.PEDGE_WIDTHS)
+def test_bwd_pedge_references(oracle, st, D):
+    """Exact group: w == loc and d/dloc == 1 bit for bit, every term and sum a multiple of 1/4 below 2^22, the fp32 restatement
+    equals the float64 one.  TOL group: the float64 restatement against the oracle's own entry points (agg_fwd on the
+    source-major view, agg_bwd_w per derivative on the forward view) and against its fp32 restatement at util.TOL."""
+    exact_spec, tol_spec = rl.pedge_specs(D)
+    T = rl.tables(D, True)
+    case = rl.Case("weights", "fwd", exact_spec, view="f")
+    assert np.array_equal(rl.weights(oracle, st, case, D), T.w) and (rl.weights(oracle, st, case, D, deriv=1) == 1.0).all()
+    dx, dp0, dp1, ab = rl.pedge_reference(oracle, st, T, exact_spec)
+    for a in (dx, dp0, ab):
+        assert np.array_equal(a * 4, np.round(a * 4)) and np.abs(a).max() < 2.0 ** 22
+    fx, f0, _, _ = rl.pedge_reference(oracle, st, T, exact_spec, f32=True)
+    assert fx.dtype == np.float32 and np.array_equal(fx.astype(np.float64), dx) and np.array_equal(f0.astype(np.float64), dp0)
+    assert np.abs(dx).max() > 0 and np.abs(dp0).max() > 0
+    T = rl.tables(D, False)
+    dx, dp0, dp1, _ = rl.pedge_reference(oracle, st, T, tol_spec)
+    assert_close(oracle.agg_fwd(st.ogs, T.x, tol_spec.o(oracle, D), src_scale=T.ss, dst_scale=T.ds), dx, what=f"D={D} dx: the oracle")
+    xs, gg = T.own * T.ds[:, None], T.x * T.ss[:, None]
+    for dv, ref in ((1, dp0), (2, dp1)):
+        got = oracle.agg_bwd_w(st.ogf, xs, gg, spec=tol_spec.o(oracle, D, deriv=dv)).astype(np.float64)
+        sc = max(1.0, float(np.abs(ref).max()))
+        assert_close(got / sc, ref / sc, what=f"D={D} dp{dv - 1}: the oracle")
+    fx, f0, f1, _ = rl.pedge_reference(oracle, st, T, tol_spec, f32=True)
+    assert_close(fx, dx, what=f"D={D} dx: the fp32 restatement")

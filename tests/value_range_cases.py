@@ -10,7 +10,11 @@ needs).  Source row U feeds the hub, the 40-, 20- and 3-edge rows and some ordin
 row of more than 16 (so that a Kahan unit never ends on it: see group C), and not the 1-edge row.
 
 A CASE names an entry point, a noise description and the launch options; `reference` gives the oracle's outputs for it,
-`numpy_reference` the same numbers from a float64 loop over the edges on the oracle's materialised weights."""
+`numpy_reference` the same numbers from a float64 loop over the edges on the oracle's materialised weights.
+
+The second half of the file ("The per-edge gradient entry points ...") holds the fixtures of
+tests/test_gpu_value_range_grad.py: GradTables, GradCase and the float64 statements grad_reference, max_fwd_reference and
+max_bwd_reference, the bars of its group B and the poison sets of its group C."""
 import numpy as np
 
 N = 48
@@ -643,3 +647,404 @@ def subnormal_bar(st, ref, kind):
     bar = 1e-5 * np.abs(np.asarray(ref, np.float64)) + 2.0 * (deg + 2.0) * TINY
     assert kind in ("rows", "mc")
     return bar
+
+
+# ======================================================================================================================
+# The per-edge gradient entry points (stag_agg_bwd_w, _bwd_w_mc, _bwd_pedge), the max reducer's backward and count, and
+# the small reductions (stag_coldot, stag_segment_reduce): tests/test_gpu_value_range_grad.py, host proofs in
+# tests/test_value_range_host.py.
+#
+# ONE LAYOUT serves the three gradient entry points, all launched on the view "t" (ogt: eid and nidx permutations):
+#   `x`     [N, D]     the table an edge GATHERS through the column id c (stag_agg_bwd_w's x with src_scale = ss;
+#                      stag_agg_bwd_pedge's g with g_scale = ss)
+#   `g_all` [S, N, D]  the rows the units OWN, one table per sample (stag_agg_bwd_w's g: sample 0, no scale of its own;
+#                      stag_agg_bwd_w_mc's g with g_scale = ds; stag_agg_bwd_pedge's x with row_scale = ds: sample 0)
+#   dw_i[eid_p, k] = sum_s D_i,s[p, k] (ss[c_p] x[c_p, k]) (ds[r_p] g_all[s, r_p, k])         (then summed over k: reduce_k)
+#   dx[r, k]       = ds[r] sum_{p in row r} w[p, k] ss[c_p] x[c_p, k]                           (stag_agg_bwd_pedge only)
+# D_i,s: the oracle's derivative weights at offset OFFSET + s GRAD_STRIDE (weights(..., deriv=i + 1)).
+# ======================================================================================================================
+GRAD_S, GRAD_STRIDE = 7, 2                 # stag_agg_bwd_w_mc, group A, C, D: passes of 4, 2 and 1 samples
+GRAD_S_SMALL = 3                           # group B: passes of 2 and 1
+GRAD_POISON_SAMPLE = 5                     # group C: in the second pass (samples 4 and 5), which reads the first one back
+V0 = ROW20                                 # group C: the owned row that is poisoned (20 in-edges; row V0 + 1 follows it)
+MARGIN = 4.0                               # group A: no intermediate of the 2^-100 launch below MARGIN 2^-126, none of
+FLT_MAX = float(np.finfo(np.float32).max)  # the 2^100 launch above FLT_MAX / MARGIN
+COLDOT_N = 300
+
+
+class GradTables:
+    """Group A's tables are kept away from zero (as x16 is): an output is a product of up to three factors, and the
+    smallest of them, a Uniform derivative u = 2^-24, must stay normal under c = 2^-100.  |x| in [1, 4), |g| in [4, 16)."""
+
+    def __init__(self, D):
+        rng = np.random.default_rng(5000 + D)
+        T = tables(D)
+        away = lambda lo, hi, shape: (rng.uniform(lo, hi, shape) * rng.choice([-1.0, 1.0], shape)).astype(np.float32)
+        self.D = D
+        self.x = away(1.0, 4.0, (N, D))
+        self.g_all = away(4.0, 16.0, (GRAD_S, N, D))
+        self.ss, self.ds = T.ss, T.ds
+        self.qlog = rng.uniform(-1.0, 0.0, (N_EDGES, D)).astype(np.float32)
+        self.gint = rng.integers(-3, 4, (N, D)).astype(np.float32)          # group B: small integers
+        self.xint = rng.integers(-2, 3, (N, D)).astype(np.float32)          # max ties: few distinct values
+        self.grand = rng.standard_normal((GRAD_S, N, D)).astype(np.float32)   # groups B (drawn), C, D: ordinary rows
+
+
+def grad_tables(D):
+    if ("GT", D) not in _CACHE:
+        _CACHE[("GT", D)] = GradTables(D)
+    return _CACHE[("GT", D)]
+
+
+class GradCase:
+    """entry: bwd_w | bwd_w_mc | bwd_pedge.  mode: "plain" (no spec: D = 1) | 1 | 2 (one derivative, spec.deriv) | "both".
+    outputs(): (name, derivative) in launch order; derivative None: D = 1, 0: the weight itself (dx)."""
+
+    def __init__(self, name, entry, spec=None, mode="both", reduce_k=False, ss=True, S=1, norm=1.0, zero=False):
+        self.name, self.entry, self.spec, self.mode, self.reduce_k, self.ss, self.S = name, entry, spec, mode, reduce_k, ss, S
+        self.norm, self.zero = norm, zero
+        assert entry in ("bwd_w", "bwd_w_mc", "bwd_pedge") and (entry == "bwd_w" or mode == "both")
+        assert (spec is None) == (mode == "plain") and (S == 1 or entry == "bwd_w_mc")
+        if entry == "bwd_pedge":
+            assert not reduce_k and spec.p0.ndim == 2 and spec.p0.shape[1] > 1
+        if entry == "bwd_w_mc":
+            assert reduce_k == (spec.p0.shape[1] == 1)
+        self.ds = entry != "bwd_w"                      # stag_agg_bwd_w's g already carries the destination scale
+
+    def outputs(self):
+        if self.entry == "bwd_pedge":
+            return [("dx", 0), ("dp0", 1), ("dp1", 2)]
+        if self.mode == "plain":
+            return [("dw", None)]
+        if self.mode == "both":
+            return [("dw0", 1), ("dw1", 2)]
+        return [(f"dw (deriv {self.mode})", self.mode)]
+
+    def kinds(self):
+        """dx: rows (the 1e-5 (1 + |ref|) bar of a sum over one row); a gradient table: relative to its largest entry"""
+        return ["rows" if d == 0 else "edge" for _, d in self.outputs()]
+
+    def norms(self):
+        """d/dloc does not carry the scale; the weight and d/dlog_scale do"""
+        return [1.0 if d in (None, 1) else self.norm for _, d in self.outputs()]
+
+
+def cases_grad_A(D):
+    GT, T, S = grad_tables(D), tables(D), Spec
+    nD, n1 = lambda: S("normal", T.q0, GT.qlog, p1_log=True), lambda: S("normal", T.e0, T.e1log, p1_log=True)
+    uD, u1 = lambda: S("uniform", T.q0, T.q0 + T.q1), lambda: S("uniform", T.e0, T.e0 + T.e1)
+    G = GradCase
+    return [
+        G("stag_agg_bwd_w no spec", "bwd_w", None, "plain"),
+        G("stag_agg_bwd_w no spec reduce_k", "bwd_w", None, "plain", reduce_k=True),
+        G("stag_agg_bwd_w [E,D] Normal p1_log d/dp0", "bwd_w", nD(), 1),
+        G("stag_agg_bwd_w [E,D] Normal p1_log d/dp1", "bwd_w", nD(), 2),
+        G("stag_agg_bwd_w [E,D] Normal p1_log both", "bwd_w", nD(), "both"),
+        G("stag_agg_bwd_w [E,1] Normal p1_log reduce_k d/dp0", "bwd_w", n1(), 1, reduce_k=True),
+        G("stag_agg_bwd_w [E,1] Normal p1_log reduce_k d/dp1", "bwd_w", n1(), 2, reduce_k=True),
+        G("stag_agg_bwd_w [E,1] Normal p1_log reduce_k both", "bwd_w", n1(), "both", reduce_k=True),
+        G("stag_agg_bwd_w [E,D] Uniform both", "bwd_w", uD(), "both"),
+        G("stag_agg_bwd_w [E,D] Uniform d/dp1", "bwd_w", uD(), 2),
+        G("stag_agg_bwd_w [E,1] Uniform reduce_k both", "bwd_w", u1(), "both", reduce_k=True),
+        G("stag_agg_bwd_w_mc [E,D] Normal p1_log", "bwd_w_mc", nD(), S=GRAD_S),
+        G("stag_agg_bwd_w_mc [E,1] Normal p1_log reduce_k", "bwd_w_mc", n1(), reduce_k=True, S=GRAD_S),
+        G("stag_agg_bwd_w_mc [E,D] Uniform", "bwd_w_mc", uD(), S=GRAD_S),
+        G("stag_agg_bwd_w_mc [E,1] Uniform reduce_k", "bwd_w_mc", u1(), reduce_k=True, S=GRAD_S),
+        G("stag_agg_bwd_pedge [E,D] Normal p1_log", "bwd_pedge", nD()),
+        G("stag_agg_bwd_pedge [E,D] Uniform", "bwd_pedge", uD()),
+    ]
+
+
+def cases_grad_B(D):
+    """Group B, drawn: Normal(1, 0.5) in [E, D] and [E, 1] tables."""
+    T, S = tables(D), Spec
+    half = np.float32(0.5)
+    nD = lambda: S("normal", np.ones_like(T.q0), np.full_like(T.q0, half))
+    n1 = lambda: S("normal", np.ones_like(T.e0), np.full_like(T.e0, half))
+    G = GradCase
+    return [
+        G("stag_agg_bwd_w [E,D] Normal both", "bwd_w", nD(), "both"),
+        G("stag_agg_bwd_w [E,1] Normal reduce_k both", "bwd_w", n1(), "both", reduce_k=True),
+        G("stag_agg_bwd_w_mc [E,D] Normal", "bwd_w_mc", nD(), S=GRAD_S_SMALL),
+        G("stag_agg_bwd_w_mc [E,1] Normal reduce_k", "bwd_w_mc", n1(), reduce_k=True, S=GRAD_S_SMALL),
+        G("stag_agg_bwd_pedge [E,D] Normal", "bwd_pedge", nD()),
+    ]
+
+
+def cases_grad_C(D):
+    """Group C: Normal tables without relu, loc from the tables, scale 0.5 (log-scale log 0.5 where p1_log)."""
+    T, S = tables(D), Spec
+    half = np.float32(0.5)
+    nD = lambda: S("normal", T.q0, np.full_like(T.q0, half))
+    nDlog = lambda: S("normal", T.q0, np.full_like(T.q0, np.log(half)), p1_log=True)
+    n1 = lambda: S("normal", T.e0, np.full_like(T.e0, half))
+    G = GradCase
+    return [
+        G("stag_agg_bwd_w no spec", "bwd_w", None, "plain"),
+        G("stag_agg_bwd_w no spec reduce_k", "bwd_w", None, "plain", reduce_k=True),
+        G("stag_agg_bwd_w [E,D] Normal d/dp1", "bwd_w", nD(), 2),
+        G("stag_agg_bwd_w [E,D] Normal p1_log both", "bwd_w", nDlog(), "both"),
+        G("stag_agg_bwd_w [E,1] Normal reduce_k both", "bwd_w", n1(), "both", reduce_k=True),
+        G("stag_agg_bwd_w_mc [E,D] Normal p1_log", "bwd_w_mc", nDlog(), S=GRAD_S),
+        G("stag_agg_bwd_w_mc [E,1] Normal reduce_k", "bwd_w_mc", n1(), reduce_k=True, S=GRAD_S),
+        G("stag_agg_bwd_pedge [E,D] Normal p1_log", "bwd_pedge", nDlog()),
+    ]
+
+
+def cases_grad_D(D):
+    T, S = tables(D), Spec
+    f = np.float32
+    z1, zD = np.zeros_like(T.e0), np.zeros_like(T.q0)
+    G = GradCase
+
+    def trio(name, sD, s1, **kw):
+        return [G(f"stag_agg_bwd_w [E,D] {name} both", "bwd_w", sD(), "both", **kw),
+                G(f"stag_agg_bwd_w [E,1] {name} reduce_k both", "bwd_w", s1(), "both", reduce_k=True, **kw),
+                G(f"stag_agg_bwd_w_mc [E,D] {name}", "bwd_w_mc", sD(), S=GRAD_S, **kw),
+                G(f"stag_agg_bwd_w_mc [E,1] {name} reduce_k", "bwd_w_mc", s1(), reduce_k=True, S=GRAD_S, **kw),
+                G(f"stag_agg_bwd_pedge [E,D] {name}", "bwd_pedge", sD(), **kw)]
+
+    out = trio("Normal(loc, 0)", lambda: S("normal", T.q0, zD), lambda: S("normal", T.e0, z1))
+    out += trio("Normal(loc, log-scale -16)", lambda: S("normal", T.q0, zD - f(16.0), p1_log=True),
+                lambda: S("normal", T.e0, z1 - f(16.0), p1_log=True))
+    out += trio("Uniform(low, low)", lambda: S("uniform", T.q0, T.q0), lambda: S("uniform", T.e0, T.e0))
+    out += trio("Normal(-2, 1) relu", lambda: S("normal", zD - f(2.0), zD + f(1.0), relu=True),
+                lambda: S("normal", z1 - f(2.0), z1 + f(1.0), relu=True))
+    out += trio("Normal(0, 0) relu", lambda: S("normal", zD, zD, relu=True), lambda: S("normal", z1, z1, relu=True), zero=True)
+    for sign in LOG_SCALES:
+        norm = float(np.exp(np.float64(sign)))
+        out += trio(f"log-scale {sign:+.0f}", lambda: S("normal", zD, log_table(sign, (N_EDGES, D)), p1_log=True),
+                    lambda: S("normal", z1, log_table(sign, (N_EDGES, 1)), p1_log=True), norm=norm)
+    return out
+
+
+def _wcase(spec):
+    return Case("weights", "fwd", spec, view="t")
+
+
+def grad_reference(O, st, gc, D, x, g_all, ss, ds, track=None, f32=False):
+    """The outputs of the case in launch order.  float64: the header's formula.  f32=True: the same in fp32, every product
+    and every sum rounded where the kernels round (ss x, ds g, their product, times the derivative; samples added in
+    increasing s from sample 0's term; the sum over k in channel order) — the emulation group B's bars are proved on.
+    track: a dict that receives lo / hi, the smallest non-zero and the largest magnitude of any intermediate."""
+    g = st.ogt
+    rows, cols, eid = st.row_of_pos, g.indices, g.eid
+    ft = np.float32 if f32 else np.float64
+    mags = []
+
+    def see(a):
+        a = np.abs(np.asarray(a, np.float64))
+        a = a[np.isfinite(a) & (a > 0)]
+        if track is not None and a.size:
+            mags.append((a.min(), a.max()))
+        return a
+
+    with np.errstate(all="ignore"):
+        a = x[cols].astype(ft)
+        if gc.ss:
+            a = (ss[cols, None].astype(ft) * a).astype(ft)
+        see(a)
+        acc = {}
+        for s in range(gc.S):
+            b = g_all[s][rows].astype(ft)
+            if gc.ds:
+                b = (ds[rows, None].astype(ft) * b).astype(ft)
+            val = (a * b).astype(ft)
+            see(b), see(val)
+            for _, d in gc.outputs():
+                if d == 0:
+                    continue
+                if d is None:
+                    term = val
+                else:
+                    Wd = weights(O, st, _wcase(gc.spec), D, deriv=d, offset=OFFSET + s * GRAD_STRIDE)[eid].astype(ft)
+                    term = (Wd * val).astype(ft)
+                see(term)
+                acc[d] = term if s == 0 else (acc[d] + term).astype(ft)
+                see(acc[d])
+        outs = []
+        for _, d in gc.outputs():
+            if d == 0:
+                W = weights(O, st, _wcase(gc.spec), D)
+                if f32:
+                    dx = np.zeros((N, D), np.float32)
+                    for p in range(N_EDGES):
+                        dx[rows[p]] += W[eid[p]] * a[p]
+                    dx = dx * ds[:, None]
+                else:
+                    dx = numpy_agg(g, x, W, ss if gc.ss else None, ds)
+                see(W[eid].astype(np.float64) * np.asarray(a, np.float64)), see(dx)
+                outs.append(dx)
+                continue
+            o = np.zeros((N_EDGES, D), ft)
+            o[eid] = acc[d]
+            if gc.reduce_k:
+                if f32:
+                    tot = np.zeros(N_EDGES, np.float32)
+                    for k in range(D):
+                        tot = tot + o[:, k]
+                    o = tot[:, None]
+                else:
+                    see(np.cumsum(o, 1))
+                    o = o.sum(1, keepdims=True)
+            see(o)
+            outs.append(o)
+    if track is not None:
+        track["lo"], track["hi"] = min(m[0] for m in mags), max(m[1] for m in mags)
+    return outs
+
+
+def grad_subnormal_bars(O, st, gc, D, g_all, ds, refs):
+    """Group B: 1e-5 |ref| + r 2^-149 f per output.
+    dw_i: a term D (ss x) (ds g) of a subnormal x is rounded r0 = 3 times on its way (ss x; times ds g; times D), each by at
+    most 2^-150, and what is later multiplied into a rounded value is ds g and D: f = max(1, |ds g|) max(1, |D|), the
+    largest over the element's terms.  Sums of subnormals are exact, a sum that reaches the normal range is rounded by at
+    most 2^-150 per addition while it stays below 2^-125: r = (r0 + 1) x the number of terms (S samples, x D with reduce_k).
+    dx: a term w (ss x) is rounded twice (f = max(1, |w|)), the block sums and the Kahan folds add at most three roundings
+    per term, the row scale one more: r = 5 indeg + 1, f = max(1, max |w|) max(1, ds)."""
+    rows, eid = st.row_of_pos, st.ogt.eid
+    bars = []
+    for (_, d), ref in zip(gc.outputs(), refs):
+        if d == 0:
+            W = np.abs(weights(O, st, _wcase(gc.spec), D).astype(np.float64))
+            f = np.ones((N, D))
+            np.maximum.at(f, rows, W[eid])
+            f *= np.maximum(1.0, ds.astype(np.float64))[:, None]
+            r = 5.0 * st.indeg[:, None] + 1.0
+        else:
+            f = np.zeros((N_EDGES, D))
+            for s in range(gc.S):
+                b = np.abs(g_all[s][rows].astype(np.float64) * (ds[rows, None] if gc.ds else 1.0))
+                Wd = np.abs(weights(O, st, _wcase(gc.spec), D, deriv=d, offset=OFFSET + s * GRAD_STRIDE)[eid].astype(np.float64))
+                f[eid] = np.maximum(f[eid], np.maximum(1.0, b) * np.maximum(1.0, Wd))
+            r = 4.0 * gc.S
+            if gc.reduce_k:
+                f, r = f.max(1, keepdims=True), r * D
+        bars.append(1e-5 * np.abs(np.asarray(ref, np.float64)) + r * TINY * f)
+    return bars
+
+
+# ---- group C: where the poison goes --------------------------------------------------------------------------------
+def poison_edge(st):
+    """EP: the edge id whose parameter row is poisoned — the hub's 11th in-edge; the row of edge EP + 1 follows it in
+    memory, and that edge belongs to another CSR row."""
+    g = st.ogt
+    return int(g.eid[g.indptr[HUB] + 10])
+
+
+def poison_sets(st, D, reduce_k):
+    """The affected sets of group C as masks over an [E, D] (or [E, 1]) gradient table, by edge id."""
+    g = st.ogt
+    cols = 1 if reduce_k else D
+    ch = [0] if reduce_k else list(POISON[D])
+    from_u, into_v0, at_ep = (np.zeros((N_EDGES, cols), bool) for _ in range(3))
+    from_u[np.ix_(st.eid_from_u, ch)] = True
+    into_v0[np.ix_(g.eid[g.indptr[V0]:g.indptr[V0 + 1]], ch)] = True
+    at_ep[poison_edge(st), ch] = True
+    return from_u, into_v0, at_ep
+
+
+def poisoned_row(a, row, D):
+    b = np.array(a, np.float32)
+    b[row, list(POISON[D])] = POISON_VALUES
+    return b
+
+
+def poisoned_param(spec, st, D, which):
+    """A copy of a Normal spec with one edge's parameters poisoned: which = "p0" (NaN) | "p1" (+inf: a log-scale, or a
+    scale), in the poisoned channels of an [E, D] table, in the edge's one entry of an [E, 1] table."""
+    p0, p1 = np.array(spec.p0, np.float32), np.array(spec.p1, np.float32)
+    ch = [0] if p0.shape[1] == 1 else list(POISON[D])
+    (p0 if which == "p0" else p1)[poison_edge(st), ch] = np.nan if which == "p0" else np.inf
+    return Spec(spec.kind, p0, p1, relu=spec.relu, p1_log=spec.p1_log)
+
+
+# ---- the max reducer: forward count and backward --------------------------------------------------------------------
+def max_fwd_reference(st, x, W):
+    """(m [E positions, D] the fp32 messages in CSR order, out, cnt) of stag_agg_max_fwd on ogt; W by edge id (None: no weight)"""
+    g = st.ogt
+    with np.errstate(all="ignore"):
+        xs = np.asarray(x, np.float32)[g.indices]
+        m = xs if W is None else (np.asarray(W, np.float32)[g.eid] * xs).astype(np.float32)
+        out = np.zeros((N, x.shape[1]), np.float32)
+        cnt = np.zeros((N, x.shape[1]), np.int32)
+        for v in range(N):
+            p = slice(g.indptr[v], g.indptr[v + 1])
+            if g.indptr[v + 1] > g.indptr[v]:
+                mv = m[p]
+                out[v] = mv.max(0)                                  # NaN if any is NaN
+                first = (mv == out[v]).argmax(0)                    # ties keep the bits of the first maximal message
+                fb = mv[first, np.arange(mv.shape[1])]
+                out[v] = np.where(np.isnan(out[v]), out[v], fb)
+                cnt[v] = (mv == out[v]).sum(0)                      # a NaN out compares equal to nothing: 0
+    return m, out, cnt
+
+
+def max_bwd_reference(st, x, W, out, cnt, gr, D0=None, D1=None, track=None):
+    """The header's three lines as a loop over the edges, in float64; [m == out] selects (a message that is not maximal
+    receives 0, whatever g holds).  Returns dx [N, D], dw [E, D] by edge id, dp0_rows, dp1_rows (zeros without D0 / D1) and
+    the ties by CSR position.  track: a list that receives every intermediate (messages, g / cnt, terms, running sums)."""
+    g = st.ogt
+    Dw = x.shape[1]
+    with np.errstate(all="ignore"):
+        m, _, _ = max_fwd_reference(st, x, W)
+        gq = np.where(cnt > 0, np.asarray(gr, np.float64) / np.maximum(cnt, 1), 0.0)
+        dx, dp0, dp1 = (np.zeros((N, Dw), np.float64) for _ in range(3))
+        dw = np.zeros((N_EDGES, Dw), np.float64)
+        tied = np.zeros((N_EDGES, Dw), bool)                        # by CSR position
+        x64 = np.asarray(x, np.float64)
+        for p in range(N_EDGES):
+            v, u, e = st.row_of_pos[p], g.indices[p], g.eid[p]
+            tie = m[p] == out[v]
+            tied[p] = tie
+            t = np.where(tie, gq[v], 0.0)
+            w = 1.0 if W is None else W[e].astype(np.float64)
+            dx[u] += w * t
+            dw[e] = x64[u] * t
+            if D0 is not None:
+                dp0[u] += D0[e].astype(np.float64) * t
+                dp1[u] += D1[e].astype(np.float64) * t
+            if track is not None:
+                track += [w * t, dw[e], dx[u].copy()] + ([D0[e] * t, D1[e] * t, dp0[u].copy(), dp1[u].copy()] if D0 is not None else [])
+        if track is not None:
+            track += [m, gq]
+    return dx, dw, dp0, dp1, tied
+
+
+def max_specs_A(D):
+    """Group A of the max reducer: the kinds stag_agg_max_bwd takes, EXPLICIT with weights of both signs"""
+    T = tables(D)
+    return {"none": Spec("none"), "explicit": Spec("explicit", T.w), "per-channel Normal": Spec("normal", T.c0, T.c1),
+            "scalar Uniform": Spec("uniform", 0.2, 1.8)}
+
+
+def planted_duplicates(st, D):
+    """Group D: EXPLICIT weights and a table x with exact duplicates of the hub's maximum planted across a segment boundary
+    at seg_len 4 — hub positions 2, 3 (segment 0), 4 (segment 1) and 41 (segment 10) carry w x = 64 in every channel, far
+    above every other message; (W by edge id, x, the four positions)."""
+    T, g = tables(D), st.ogt
+    W = np.array(T.wpos, np.float32)
+    x = np.array(T.x, np.float32)
+    pos = g.indptr[HUB] + np.array([2, 3, 4, 41])
+    srcs = g.indices[pos]
+    x[srcs] = 8.0
+    W[g.eid[pos]] = 8.0
+    return W, x, pos
+
+
+# ---- stag_coldot, stag_segment_reduce -------------------------------------------------------------------------------
+SEGMENT_OFFSETS = np.array([0, 0, 1, 4, 8, 13, 13, 22, 39, 48, 48], np.int32)      # empty, 1, 3, 4, 5, empty, 9, 17, 9, empty
+
+
+def coldot_big_n(D):
+    """a row count past the second grid-stride trip of stag_coldot's first stage: 1024 blocks x R rows, twice, and some"""
+    elems = D // 4 if D % 4 == 0 else D
+    cw = 1
+    while cw < elems and cw < 256:
+        cw <<= 1
+    return 2 * 1024 * (256 // cw) + 37
+
+
+def away_table(seed, shape, lo=1.0, hi=4.0):
+    rng = np.random.default_rng(seed)
+    return (rng.uniform(lo, hi, shape) * rng.choice([-1.0, 1.0], shape)).astype(np.float32)
