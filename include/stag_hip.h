@@ -891,6 +891,58 @@ typedef struct stag_gat_drop {
   const uint64_t* epoch;    /* device counter added to offset when the kernel runs, or NULL (as stag_noise_spec) */
 } stag_gat_drop;
 
+/* ---- the node block between two layers: BatchNorm1d + ReLU + Dropout on rows [n_rows, D] as fused passes (every arxiv
+ * script of the reference: scripts/arxiv_mle/(all)/run.py:89-119), additive in v19 ----
+ *     xhat = (x - mean) * rstd;   pre = xhat * gamma + beta;   y = relu(pre) * m / keep_prob
+ * each operation rounded to fp32 (nothing is contracted), gamma NULL: 1, beta NULL: 0, relu == 0: y = pre * m / keep_prob.
+ * m[n, k] (drop not NULL and keep_prob < 1; else 1) is the BERNOULLI draw of the noise stream above with probs =
+ * keep_prob at gpos = n, chunk = k / 4, under (seed, offset + *epoch): the field stag_noise_materialize writes for that
+ * spec on the n_rows-edge identity graph.  The backward draws it again; no mask is stored.
+ * stag_node_norm_stats: mean_out[k] and rstd_out[k] = 1 / sqrt(var[k] + eps) of the columns of x, var the biased
+ *   variance.  A workgroup takes a slab of rows whose size depends on n_rows alone (64 up to 131,072 rows, then the
+ *   power of two that leaves at most 2048 slabs) and leaves (mean, M2) of its rows per channel in `workspace`, from the
+ *   sums of x - K and (x - K)^2 with K the slab's first row; a second small launch merges 8 runs of consecutive slabs in
+ *   slab order, then the 8 runs in order, by Chan's formula.  running_mean / running_var (each may be NULL) become
+ *   (1 - momentum_factor) * running + momentum_factor * (mean | var * n_rows / (n_rows - 1)); with n_rows == 1 the
+ *   biased 0 goes into running_var.
+ * stag_node_norm_fwd: one elementwise pass with the mean / rstd handed over (the batch's, or 1 / sqrt(running_var +
+ *   eps) formed by the caller).
+ * stag_node_norm_bwd: with g' = g * m / keep_prob * [pre > 0] (the bracket only with relu; pre formed again from x and
+ *   the four [D] vectors by the forward's own operations, so the decision is the forward's bit for bit):
+ *     dbeta[k] = sum_n g'[n, k];   dgamma[k] = sum_n g'[n, k] * xhat[n, k]
+ *     dx = gamma * rstd * (g' - dbeta / n_rows - xhat * dgamma / n_rows)     batch_stats != 0
+ *     dx = gamma * rstd * g'                                                  batch_stats == 0 (running statistics)
+ *   dx, dgamma, dbeta may each be NULL.  The two sums come from the slab scheme above (plain fp32 sums inside a slab,
+ *   Kahan-compensated across the slabs) in two launches that are skipped when neither a sum nor a batch-statistics dx is
+ *   asked for; the merge launch writes dgamma and dbeta; a third launch forms g' again and writes dx.
+ * No atomics and no arrival counters anywhere: every result is a function of (n_rows, D, the data) alone and two calls
+ * give the same bits.  A team of lanes per row, 4 channels a lane: 16-byte loads and stores when D % 4 == 0 and the rows
+ * are 16-byte aligned (pointer and stride), scalar forms otherwise.  Rows take 64-bit addresses: n_rows * ld * 4 may pass
+ * 2^32.  workspace: >= stag_node_norm_workspace_bytes(n_rows, D) bytes, one size for the statistics and the backward.
+ * Checked in this order, before any device work:
+ * STAG_EINVAL: D <= 0; n_rows < 0; drop with keep_prob outside (0, 1] or rows / chunks outside the counter space
+ *   (n_rows > 2^44, ceil(D / 4) > 2^20); a row stride smaller than D; eps not positive and finite; a momentum_factor
+ *   that is not finite next to a running buffer; then, with n_rows > 0, a NULL x / mean / rstd / mean_out / rstd_out /
+ *   y / g, or a NULL workspace where one is read (the statistics; a backward that forms the sums).
+ * STAG_ENOSYS: n_rows > 2^34 or ceil(D / 4) > 2^20 (the launch grids end there).
+ * STAG_ENOMEM: workspace_bytes too small.  n_rows == 0 returns STAG_OK after the shape checks and writes nothing. */
+typedef struct stag_node_drop {   /* the layout of stag_gat_drop */
+  float keep_prob;          /* 1 - p, in (0, 1] */
+  uint64_t seed, offset;
+  const uint64_t* epoch;    /* device counter added to offset when the kernel runs, or NULL */
+} stag_node_drop;
+size_t stag_node_norm_workspace_bytes(int64_t n_rows, int32_t D);
+int stag_node_norm_stats(const float* x, int64_t ldx, int64_t n_rows, int32_t D, float eps,
+                         float* mean_out, float* rstd_out, float* running_mean, float* running_var,
+                         float momentum_factor, void* workspace, size_t workspace_bytes, void* stream);
+int stag_node_norm_fwd(const float* x, int64_t ldx, int64_t n_rows, int32_t D,
+                       const float* mean, const float* rstd, const float* gamma, const float* beta, int32_t relu,
+                       const stag_node_drop* drop, float* y, int64_t ldy, void* stream);
+int stag_node_norm_bwd(const float* x, int64_t ldx, const float* g, int64_t ldg, int64_t n_rows, int32_t D,
+                       const float* mean, const float* rstd, const float* gamma, const float* beta, int32_t relu,
+                       const stag_node_drop* drop, int32_t batch_stats, float* dx, int64_t lddx,
+                       float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+
 /* GAT edge attention with noisy logits + softmax + aggregation, one launch:
  *   e[p,h]  = w[p,h] * leaky_relu(el[u_p,h] + er[v,h])     stag/zoo/gat.py:114-119
  *   a[p,h]  = softmax over the in-edges of v                stag/zoo/gat.py:122

@@ -47,6 +47,10 @@ class GatDrop(C.Structure):       # stag_gat_drop
     _fields_ = [("keep_prob", C.c_float), ("seed", C.c_uint64), ("offset", C.c_uint64), ("epoch", C.c_void_p)]
 
 
+class NodeDrop(C.Structure):      # stag_node_drop
+    _fields_ = GatDrop._fields_
+
+
 class Plan(C.Structure):
     _fields_ = [("seg_len", C.c_int32), ("n_units", C.c_int32), ("n_long", C.c_int32),
                 ("n_seg", C.c_int32), ("units", _vp), ("long_rows", _vp), ("long_seg_ptr", _vp),
@@ -169,7 +173,15 @@ def bind(path):
     l.stag_edge_embed_fwd.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp, C.c_int64, _vp]
     l.stag_edge_embed_bwd.argtypes = [C.POINTER(Csr), C.POINTER(Plan), _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp,
                                       C.c_int64, _vp, C.c_int64, _vp]
-    l.stag_normal_kl_fwd.argtypes = [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
+    l.stag_node_norm_workspace_bytes.restype = C.c_size_t
+    l.stag_node_norm_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    l.stag_node_norm_stats.argtypes = [_vp, C.c_int64, C.c_int64, C.c_int32, C.c_float, _vp, _vp, _vp, _vp, C.c_float,
+                                       _vp, C.c_size_t, _vp]
+    l.stag_node_norm_fwd.argtypes = [_vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
+                                     C.POINTER(NodeDrop), _vp, C.c_int64, _vp]
+    l.stag_node_norm_bwd.argtypes = [_vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
+                                     C.POINTER(NodeDrop), C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp]
+    l.stag_normal_kl_fwd.argtypes =[_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     l.stag_normal_kl_bwd.argtypes = [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     l.stag_sample_kl_workspace_bytes.restype = C.c_size_t
     l.stag_sample_kl_workspace_bytes.argtypes = [C.c_int64, C.c_int32]

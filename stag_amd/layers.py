@@ -308,14 +308,21 @@ class StagLayer(torch.nn.Module):
 
 
 class FeatOnlyLayer(torch.nn.Module):
-    """Apply a dense module, ignore the graph (stag/layers.py:147-154)."""
+    """Apply a dense module, ignore the graph (stag/layers.py:147-154).  The block of the arxiv scripts —
+    Sequential(BatchNorm1d[, ReLU][, Dropout]) on [N, D] fp32 rows — runs as fused HIP passes (ops.node_block) where
+    ops.node_block_why_not has no objection; its dropout mask then counts the offsets of `generator`
+    (random.node_generator when None), never those of the edge-noise stream."""
     vi = False
 
-    def __init__(self, layer):
+    def __init__(self, layer, generator: Union[None, _random.NoiseGenerator] = None):
         super().__init__()
         self.layer = layer
+        self.generator = generator
 
     def forward(self, graph, feat):
+        from . import ops
+        if ops.node_block_why_not(self.layer, feat) is None:
+            return ops.node_block(feat, *ops.node_block_parts(self.layer), generator=self.generator)
         return self.layer(feat)
 
 

@@ -825,6 +825,181 @@ def edge_embed(graph, p_src, p_dst):
     return _EdgeEmbed.apply(p_src, p_dst, graph)
 
 
+# ---- the node block between two layers: BatchNorm1d (+ ReLU) (+ Dropout) on [N, D] rows as fused passes ---------------
+# FeatOnlyLayer(Sequential(BatchNorm1d(hidden), ReLU(), Dropout(0.5))) of every arxiv script is eight torch launches
+# forward and backward; here it is two small-output reductions and one elementwise pass forward, and the same again
+# plus nothing saved but x backward.  With the switch on, the block's dropout mask comes from random.node_generator's
+# counters (the project's Bernoulli draw), not from torch's generator: the same law, another mask for a given seed.
+# tools/node_block_time.py holds the switch to the project's rule: max(f, f') <= mean(c, c') + |c - c'| in every case.
+# MI355X, training block with Dropout(0.5), torch / fused (profiles/r26/node_block.txt): forward 255 / 126 us at
+# [169,343, 128], 542 / 173 at [169,343, 256], 318 / 86 at [56,944, 256]; forward + backward 576 / 263, 1258 / 403, 690 / 177;
+# peak allocation of a step 248 / 84, 498 / 169, 168 / 58 MiB; the arxiv GCN epoch 3.27 -> 2.62 ms, GraphSAGE 4.03 -> 3.39.
+# The Cora-sized [2,708, 16] is bound by the host's calls, not the device, and misses the rule: 46 / 57 us forward, 115 /
+# 135 forward + backward.  One missed case ships the switch off; turn it on for the arxiv- and PPI-sized models.
+NODE_BLOCK_FUSED = False
+
+
+def node_block_parts(module):
+    """(BatchNorm1d, ReLU | None, Dropout | None) when module is exactly a Sequential of BatchNorm1d, then optionally
+    ReLU, then optionally Dropout (the classes themselves: a subclass may compute anything), else None."""
+    if type(module) is not torch.nn.Sequential:
+        return None
+    mods = list(module)
+    if not mods or type(mods[0]) is not torch.nn.BatchNorm1d:
+        return None
+    bn, rest, relu, dropout = mods[0], mods[1:], None, None
+    if rest and type(rest[0]) is torch.nn.ReLU:
+        relu, rest = rest[0], rest[1:]
+    if rest and type(rest[0]) is torch.nn.Dropout:
+        dropout, rest = rest[0], rest[1:]
+    if rest:
+        return None
+    if any(t is not None and t.dtype != torch.float32 for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
+        return None
+    return bn, relu, dropout
+
+
+def node_block_why_not(module, x):
+    """The first reason FeatOnlyLayer keeps the torch route for `module` on x, or None: stag_node_norm_stats / _fwd and,
+    under autograd, _bwd run the block.  One clause per case that has no fused form.  (A double backward cannot be seen
+    from here: _NodeBlock is once_differentiable and raises in one; turn the switch off for it.)"""
+    if not NODE_BLOCK_FUSED:
+        return "switch"
+    parts = node_block_parts(module)
+    if parts is None:
+        return "module"
+    bn, _relu, dropout = parts
+    if x.dim() != 2 or x.shape[1] != bn.num_features:       # ([N, C, L] is out of scope; a wrong width is torch's to refuse)
+        return "shape"
+    if x.dtype != torch.float32:
+        return "dtype"
+    if not x.is_cuda:
+        return "device"
+    if x.shape[0] < (2 if (bn.training or bn.running_mean is None) else 1):   # torch raises on one training row: let it
+        return "rows"
+    if dropout is not None and dropout.p >= 1:
+        return "dropout"
+    if torch.compiler.is_compiling():
+        return "compiling"
+    if torch.cuda.is_current_stream_capturing():            # the host counter of the mask's generator would freeze
+        return "capturing"
+    return None
+
+
+def _node_drop_struct(drop):
+    """(p, seed, offset, epoch tensor | None) -> stag_node_drop, or None"""
+    if drop is None:
+        return None
+    d = _lib.NodeDrop()
+    d.keep_prob = 1.0 - float(drop[0])
+    d.seed, d.offset = int(drop[1]) & _MASK64, int(drop[2]) & _MASK64
+    d.epoch = _lib.ptr(drop[3])
+    return d
+
+
+def _node_ws(n, D, dev):
+    nbytes = _lib.lib().stag_node_norm_workspace_bytes(n, D)
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=dev), nbytes
+
+
+def _node_stats_raw(x, eps, running_mean=None, running_var=None, factor=0.0):
+    """One stag_node_norm_stats: (mean, rstd) [D] of the columns of x; the running buffers are updated in place."""
+    dev = _lib.require_device(x, running_mean, running_var)
+    n, D = x.shape
+    mean = torch.empty(D, dtype=torch.float32, device=dev)
+    rstd = torch.empty(D, dtype=torch.float32, device=dev)
+    ws, nbytes = _node_ws(n, D, dev)
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_node_norm_stats(_lib.ptr(x), max(x.stride(0), D), n, D, eps, _lib.ptr(mean), _lib.ptr(rstd),
+                                             _lib.ptr(running_mean), _lib.ptr(running_var), factor, _lib.ptr(ws), nbytes,
+                                             _lib.stream_of(dev))
+    _lib.check(rc, "stag_node_norm_stats")
+    return mean, rstd
+
+
+def _node_fwd_raw(x, mean, rstd, gamma, beta, relu, drop, out=None):
+    """One stag_node_norm_fwd on fp32 rows (_rows32)."""
+    dev = _lib.require_device(x, mean, rstd, gamma, beta)
+    n, D = x.shape
+    y = torch.empty((n, D), dtype=torch.float32, device=dev) if out is None else out
+    d = _node_drop_struct(drop)
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_node_norm_fwd(_lib.ptr(x), max(x.stride(0), D), n, D, _lib.ptr(mean), _lib.ptr(rstd),
+                                           _lib.ptr(gamma), _lib.ptr(beta), int(relu), C.byref(d) if d is not None else None,
+                                           _lib.ptr(y), max(y.stride(0), D), _lib.stream_of(dev))
+    _lib.check(rc, "stag_node_norm_fwd")
+    return y
+
+
+def _node_bwd_raw(x, g, mean, rstd, gamma, beta, relu, drop, batch_stats, want_dx=True, want_dgamma=True, want_dbeta=True):
+    """One stag_node_norm_bwd: (dx [N, D], dgamma [D], dbeta [D]), None for what was not asked for."""
+    dev = _lib.require_device(x, g, mean, rstd, gamma, beta)
+    n, D = x.shape
+    dx = torch.empty((n, D), dtype=torch.float32, device=dev) if want_dx else None
+    dgamma = torch.empty(D, dtype=torch.float32, device=dev) if want_dgamma else None
+    dbeta = torch.empty(D, dtype=torch.float32, device=dev) if want_dbeta else None
+    ws, nbytes = _node_ws(n, D, dev)
+    d = _node_drop_struct(drop)
+    with _lib.on_device(dev):
+        rc = _lib.lib().stag_node_norm_bwd(_lib.ptr(x), max(x.stride(0), D), _lib.ptr(g), max(g.stride(0), D), n, D,
+                                           _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gamma), _lib.ptr(beta), int(relu),
+                                           C.byref(d) if d is not None else None, int(batch_stats), _lib.ptr(dx), D,
+                                           _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws), nbytes, _lib.stream_of(dev))
+    _lib.check(rc, "stag_node_norm_bwd")
+    return dx, dgamma, dbeta
+
+
+class _NodeBlock(torch.autograd.Function):
+    """y = dropout(relu(batch_norm(x))) from one elementwise pass over x (stag_node_norm_fwd) with the statistics handed
+    over.  Saved: x, the [D] vectors mean, rstd, gamma, beta and the drop record (p, seed, offset, epoch) — nothing
+    [N, D]-sized besides x: the backward (stag_node_norm_bwd) forms the pre-activation and draws the mask again."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, gamma, beta, mean, rstd, batch_stats, relu, drop):
+        ctx.save_for_backward(x, gamma, beta, mean, rstd)
+        ctx.batch_stats, ctx.relu, ctx.drop = batch_stats, relu, drop
+        return _node_fwd_raw(x, mean, rstd, gamma, beta, relu, drop)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, gamma, beta, mean, rstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dgamma, dbeta = _node_bwd_raw(x, _rows32(g), mean, rstd, gamma, beta, ctx.relu, ctx.drop, ctx.batch_stats,
+                                          want_dx=need[0], want_dgamma=gamma is not None and need[1],
+                                          want_dbeta=beta is not None and need[2])
+        return dx, dgamma, dbeta, None, None, None, None, None
+
+
+def node_block(x, bn, relu=None, dropout=None, generator=None):
+    """Dropout(ReLU(BatchNorm1d(x))) on x [N, D] with the modules' own parameters, buffers and modes: what
+    Sequential(bn, relu, dropout)(x) computes (relu, dropout: the module or None), with torch.nn.BatchNorm1d's buffer
+    updates.  A live dropout takes one offset of `generator` (random.node_generator) for its mask.
+    node_block_why_not says when FeatOnlyLayer takes it."""
+    from . import random as _random
+    batch_stats = bn.training or bn.running_mean is None
+    drop = None
+    if dropout is not None and dropout.training and dropout.p > 0:
+        gen = generator if generator is not None else _random.node_generator
+        drop = (float(dropout.p), gen.seed ^ _random.NODE_DROP_DOMAIN, gen.next_offset(), gen.device_epoch)
+    xr = _rows32(x)
+    with torch.no_grad():
+        if batch_stats:
+            rm = rv = None
+            factor = 0.0
+            if bn.training and bn.running_mean is not None:
+                rm, rv = bn.running_mean, bn.running_var
+                if bn.num_batches_tracked is not None:
+                    bn.num_batches_tracked.add_(1)
+                factor = float(bn.momentum) if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+            mean, rstd = _node_stats_raw(xr, float(bn.eps), rm, rv, factor)
+        else:
+            mean, rstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)
+    return _NodeBlock.apply(xr, bn.weight, bn.bias, mean, rstd, batch_stats, relu is not None, drop)
+
+
 class _NormalKlMean(torch.autograd.Function):
     """mean over all elements of KL(N(loc, exp(log_scale)) || N(p_loc, p_scale)) with one-element prior parameters
     (torch.distributions.kl._kl_normal_normal; stag/layers.py:132-145): one pass forward, one backward, against

@@ -14,6 +14,8 @@ _MASK64 = (1 << 64) - 1
 # xor-ed into the seed of streams that are not edge noise (GAT's attention-dropout mask): same generator, same
 # offset counter, a different key — the two can never draw from one (seed, offset) pair
 ATTN_DROP_DOMAIN = 0xA77D209D0F5EED55
+# ... and into the seed of the dropout mask of a node block (ops.node_block), drawn from node_generator below
+NODE_DROP_DOMAIN = 0x40DED209B10C5EED
 
 
 class NoiseGenerator:
@@ -71,8 +73,13 @@ class NoiseGenerator:
 
 
 default_generator = NoiseGenerator(seed=0x5747A6)
+# The dropout masks of the fused node blocks (layers.FeatOnlyLayer) count their offsets here, one per training forward:
+# models.StagModel counts the offsets of default_generator per Monte-Carlo sample (offsets_per_forward), and a block
+# that drew from that stream would switch the batched first layer off for every model.
+node_generator = NoiseGenerator(seed=0x5747A6)
 
 
 def manual_seed(seed):
-    """Seed the edge-noise stream (all ranks of a partitioned run must use one seed)."""
+    """Seed the edge-noise stream (all ranks of a partitioned run must use one seed) and the node blocks' mask stream."""
+    node_generator.manual_seed(seed)
     return default_generator.manual_seed(seed)
