@@ -943,6 +943,57 @@ int stag_node_norm_bwd(const float* x, int64_t ldx, const float* g, int64_t ldg,
                        const stag_node_drop* drop, int32_t batch_stats, float* dx, int64_t lddx,
                        float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the likelihood end of the objective: the masked mean of the negative log-likelihood of Categorical(probs) or
+ * Bernoulli(probs) over rows probs [n_rows, C], and its gradient, as fused passes (stag/models.py:69-76 with
+ * stag/likelihoods.py: every script of the reference), additive in v19 ----
+ * torch's arithmetic, as Categorical(probs=..., validate_args=False) and Bernoulli(probs=...) compute it, eps = 2^-23:
+ *   categorical, a row n inside the mask (mask NULL: every row; else one byte per row, non-zero = inside):
+ *     s = sum_c p[n,c];   q = p[n,y_n] / s;   nll_n = -log(min(max(q, eps), 1 - eps))
+ *     value = sum_{n in mask} nll_n / count;   denom = count
+ *     dprobs[n,c] = -(g / count) * [eps <= q <= 1 - eps] * ([c == y_n] / p[n,y_n] - 1 / s)
+ *   Bernoulli, every element of a row inside the mask (y fp32 of the shape of probs):
+ *     pc = min(max(p, eps), 1 - eps);   nll = -(y * log(pc) + (1 - y) * log1p(-pc))
+ *     value = sum / (count * C);   denom = count * C
+ *     dprobs = (g / denom) * [eps <= p <= 1 - eps] * (-y / pc + (1 - y) / (1 - pc))
+ * Outside the clamp window the gradient is 0 (p_y = 0 included: nothing divides there).  Rows outside the mask are not
+ * read in the forward (a row costs its mask byte) and get zero rows in dprobs; dprobs may arrive uninitialised, every
+ * element of its n_rows x C is written.  g and denom ([1] each, the forward's denom) are read on the device: no host
+ * read anywhere, and the calls are capturable in a hipGraph.
+ * Edges: count == 0 gives value = NaN (0 / 0, the mean of nothing) and an all-zero dprobs.  A NaN in a masked row makes
+ * value NaN.  A label outside [0, C) in a masked row makes value NaN and that row's gradient 0, and no address outside
+ * the row is ever formed (torch device-asserts there).
+ * A team of T lanes per row, T the smallest power of two with 4 T >= C, at most 64: 64 / T rows a wave, 4 channels a
+ * lane, further channel tiles in a loop when C > 256; 16-byte loads and stores when C % 4 == 0 and the rows are 16-byte
+ * aligned (pointer and stride), scalar forms otherwise.  The row sum is a fixed xor butterfly inside the team.  Forward:
+ * a workgroup takes a slab of rows whose size depends on n_rows alone (64 up to 131,072 rows, then the power of two that
+ * leaves at most 2048 slabs); the row terms fold team (row order) -> wave (butterfly over the teams) -> workgroup (wave
+ * order) and (sum, count) of the slab goes to `workspace`; a one-workgroup merge launch adds the slab partials in double,
+ * thread t its run of consecutive slabs in slab order, then the 256 runs by a fixed halving tree, and writes value and
+ * denom.  No atomics and no arrival counters: the result is a function of (n_rows, C, the data) alone and two calls
+ * give the same bits.  The backward is one elementwise launch that forms s again from the row.  Rows take 64-bit
+ * offsets: n_rows * ld * 4 may pass 2^32.  workspace: >= stag_nll_workspace_bytes(n_rows, C) bytes (forward only).
+ * Checked in this order, before any device work:
+ * STAG_EINVAL: C <= 0; n_rows < 0; a row stride (ldp, ldy, lddp) smaller than C; then, with n_rows > 0, a NULL probs /
+ *   y / value / denom / g / dprobs, or a NULL workspace in a forward.
+ * STAG_ENOSYS: n_rows > 2^34 (the backward's grid ends there: 16 rows or more a workgroup) or C > 2^30 (the channel
+ *   loops count in 32 bits).
+ * STAG_ENOMEM: workspace_bytes too small.  n_rows == 0 then returns STAG_OK and writes nothing. */
+size_t stag_nll_workspace_bytes(int64_t n_rows, int32_t C);
+int stag_nll_categorical_fwd(const float* probs, int64_t ldp, int64_t n_rows, int32_t C,
+                             const int64_t* y, const uint8_t* mask /* NULL: every row */,
+                             float* value /* [1] */, float* denom /* [1] */,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int stag_nll_categorical_bwd(const float* probs, int64_t ldp, int64_t n_rows, int32_t C,
+                             const int64_t* y, const uint8_t* mask,
+                             const float* g /* [1], device */, const float* denom /* [1], device */,
+                             float* dprobs, int64_t lddp, void* stream);
+int stag_nll_bernoulli_fwd(const float* probs, int64_t ldp, const float* y, int64_t ldy, int64_t n_rows, int32_t C,
+                           const uint8_t* mask, float* value, float* denom,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int stag_nll_bernoulli_bwd(const float* probs, int64_t ldp, const float* y, int64_t ldy, int64_t n_rows, int32_t C,
+                           const uint8_t* mask, const float* g, const float* denom,
+                           float* dprobs, int64_t lddp, void* stream);
+
 /* GAT edge attention with noisy logits + softmax + aggregation, one launch:
  *   e[p,h]  = w[p,h] * leaky_relu(el[u_p,h] + er[v,h])     stag/zoo/gat.py:114-119
  *   a[p,h]  = softmax over the in-edges of v                stag/zoo/gat.py:122

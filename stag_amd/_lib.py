@@ -181,6 +181,14 @@ def bind(path):
                                      C.POINTER(NodeDrop), _vp, C.c_int64, _vp]
     l.stag_node_norm_bwd.argtypes = [_vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
                                      C.POINTER(NodeDrop), C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp]
+    l.stag_nll_workspace_bytes.restype = C.c_size_t
+    l.stag_nll_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    l.stag_nll_categorical_fwd.argtypes = [_vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
+    l.stag_nll_categorical_bwd.argtypes = [_vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]
+    l.stag_nll_bernoulli_fwd.argtypes = [_vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp,
+                                         C.c_size_t, _vp]
+    l.stag_nll_bernoulli_bwd.argtypes = [_vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp,
+                                         C.c_int64, _vp]
     l.stag_normal_kl_fwd.argtypes =[_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     l.stag_normal_kl_bwd.argtypes = [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     l.stag_sample_kl_workspace_bytes.restype = C.c_size_t

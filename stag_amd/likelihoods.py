@@ -30,6 +30,21 @@ class Likelihood(torch.nn.Module, abc.ABC):
     def log_prob(self, feat, y):
         return self.condition(feat).log_prob(y)
 
+    def mean_nll(self, feat, y, mask=None):
+        """(-log_prob(feat, y))[mask].mean(), the likelihood term of the objective (stag/models.py:73-76), composed from
+        this object's own log_prob: a subclass that overrides log_prob or condition keeps its meaning."""
+        from .models import _masked_mean
+        return _masked_mean(-self.log_prob(feat, y), mask)
+
+
+def _fused_mean_nll(likelihood, feat, y, mask):
+    """The masked mean NLL of one of the two shipped classes: one fused pass each way where ops.nll_why_not has no
+    objection (stag_nll_categorical_fwd / _bwd, stag_nll_bernoulli_fwd / _bwd), else the composed expression."""
+    from . import ops
+    if ops.nll_why_not(likelihood, feat, y, mask) is None:
+        return ops.nll_mean(likelihood, feat, y, mask)
+    return Likelihood.mean_nll(likelihood, feat, y, mask)
+
 
 class CategoricalLikelihood(Likelihood):
     def __init__(self):
@@ -38,6 +53,9 @@ class CategoricalLikelihood(Likelihood):
     def condition(self, feat):
         return self.distribution(probs=feat, validate_args=_validate(feat))
 
+    def mean_nll(self, feat, y, mask=None):
+        return _fused_mean_nll(self, feat, y, mask)
+
 
 class BernoulliLikelihood(Likelihood):
     def __init__(self):
@@ -45,3 +63,6 @@ class BernoulliLikelihood(Likelihood):
 
     def condition(self, feat):
         return self.distribution(probs=feat, validate_args=_validate(feat))
+
+    def mean_nll(self, feat, y, mask=None):
+        return _fused_mean_nll(self, feat, y, mask)

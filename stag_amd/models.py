@@ -46,6 +46,15 @@ def _masked_mean(nll, mask):
     return nll[mask].mean()
 
 
+def _mean_nll(likelihood, out, y, mask):
+    """The likelihood term of one Monte-Carlo sample: likelihood.mean_nll where it has one (the shipped classes take the
+    fused head there, ops.nll_why_not), else the two lines of stag/models.py:73-76 on its log_prob."""
+    if hasattr(likelihood, "mean_nll"):
+        return likelihood.mean_nll(out, y, mask)
+    nll = -likelihood.log_prob(out, y)
+    return _masked_mean(nll, mask)
+
+
 def _is_identity(module):
     """True for a dense module that returns its input in its current mode: torch.nn.Identity, a Dropout that is off
     (eval mode, or p == 0), or a Sequential of only such modules."""
@@ -173,8 +182,7 @@ class StagModel(torch.nn.Module):
         kl_scaling = self.kl_scaling if kl_scaling is None else kl_scaling
         total_nll = total_reg = 0.0
         for out in self._mc_outputs(graph, feat, n_samples):
-            nll = -self.likelihood.log_prob(out, y)
-            total_nll = total_nll + _masked_mean(nll, mask)
+            total_nll = total_nll + _mean_nll(self.likelihood, out, y, mask)
             total_reg = total_reg + self._regulariser()
         return total_nll / n_samples, total_reg / n_samples * kl_scaling
 
@@ -205,7 +213,6 @@ class StagModelContrastive(StagModel):
         total_nll = total_reg = 0.0
         for _ in range(n_samples):
             out, contrastive = self._forward(graph, feat)
-            nll = -self.likelihood.log_prob(out, y)
-            total_nll = total_nll + _masked_mean(nll, mask)
+            total_nll = total_nll + _mean_nll(self.likelihood, out, y, mask)
             total_reg = total_reg + contrastive + self._regulariser()
         return total_nll / n_samples, total_reg / n_samples * kl_scaling

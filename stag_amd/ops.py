@@ -1047,6 +1047,171 @@ def normal_kl_mean(loc, log_scale, p_loc, p_scale):
     return _NormalKlMean.apply(loc, log_scale, p_loc, p_scale)
 
 
+# ---- the likelihood end of the objective: the masked mean NLL of model.loss as fused passes (csrc/nll.hip) -------------
+# -likelihood.log_prob(out, y) and models._masked_mean are ~12 torch launches forward over [N, C] (row sum, divide,
+# clamp, log, gather, negate, where, sum, mask.sum, divide) and as many again backward, once per Monte-Carlo sample;
+# stag_nll_categorical_fwd / _bwd and stag_nll_bernoulli_fwd / _bwd are two launches forward (slab partials, merge) and
+# one backward, read only the rows inside the mask and keep nothing [N, C]-sized but the probabilities.
+# tools/loss_head_time.py holds the switch to the project's rule: max(f, f') <= mean(c, c') + |c - c'| in every case.
+# MI355X, composed / fused (profiles/r27/loss_head.txt), forward and forward + backward in us: Categorical [169,343, 40]
+# with a 0.54 mask 98 / 29 and 307 / 97, without a mask 73 / 27 and 239 / 73; Cora [2,708, 7] with 140 masked rows 78 / 27
+# and 274 / 80; Pubmed [19,717, 3] with 60 rows 80 / 27 and 283 / 80; a readout batch [128, 10] 45 / 25 and 210 / 75;
+# Bernoulli [56,944, 121] 161 / 43 and 323 / 75 (the worse of two repeats of the fused route against the mean of two of
+# the composed one, which differ by 0 - 8 us).  The small cases are bound by the host's calls on both routes: 3 launches
+# against ~25.  Peak allocation of a step at the arxiv shape 105 / 0 MiB over the gradient, 131 / 0 at the PPI shape.
+# Whole steps, switch off / on: the arxiv GCN epoch 3.26 / 3.00 ms, a Cora-sized two-layer GCN step 0.98 / 0.72 ms.
+# Every case meets the rule: the switch ships on.
+NLL_FUSED = True
+
+
+def _nll_kind(likelihood):
+    """"categorical" | "bernoulli" for exactly the two shipped classes over their original torch distribution (a
+    subclass may compute anything), else None."""
+    from . import likelihoods as _lk
+    if type(likelihood) is _lk.CategoricalLikelihood and likelihood.distribution is torch.distributions.Categorical:
+        return "categorical"
+    if type(likelihood) is _lk.BernoulliLikelihood and likelihood.distribution is torch.distributions.Bernoulli:
+        return "bernoulli"
+    return None
+
+
+def _nll_form_why_not(likelihood, feat, y, mask):
+    from . import likelihoods as _lk
+    kind = _nll_kind(likelihood)
+    if kind is None:
+        return "likelihood"
+    if _lk.VALIDATE_ON_DEVICE:                                # torch's argument check is wanted: only torch runs it
+        return "validating"
+    if not torch.is_tensor(y) or not hasattr(feat, "dim"):
+        return "labels"
+    if not feat.is_cuda:
+        return "device"
+    if feat.dtype != torch.float32:
+        return "dtype"
+    if feat.dim() != 2 or feat.shape[0] == 0 or feat.shape[1] == 0:
+        return "shape"
+    n, C_ = feat.shape
+    if feat.stride(1) != 1 or feat.stride(0) < C_:
+        return "stride"
+    if y.device != feat.device:
+        return "labels"
+    if kind == "categorical":
+        if y.dtype != torch.int64 or tuple(y.shape) != (n,):             # (int32 or float labels: torch's to take)
+            return "labels"
+    elif y.dtype != torch.float32 or y.shape != feat.shape or y.stride(1) != 1 or y.stride(0) < C_:
+        return "labels"
+    if mask is not None and (not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (n,)):
+        return "mask"                                         # (an index tensor, a weight: nll[mask] gives it a meaning)
+    if y.requires_grad:
+        return "label gradient"
+    if torch.compiler.is_compiling():
+        return "compiling"
+    return None
+
+
+def nll_why_not(likelihood, feat, y, mask=None):
+    """The first reason Likelihood.mean_nll keeps the composed route (-log_prob, then models._masked_mean) for feat
+    [N, C], labels y and mask, or None: one stag_nll_*_fwd gives the masked mean and, under autograd, one stag_nll_*_bwd
+    its gradient.  One clause per case that has no fused form.  A host mask is fine: it is moved to the device, as
+    _masked_mean moves it."""
+    if not NLL_FUSED:
+        return "switch"
+    return _nll_form_why_not(likelihood, feat, y, mask)
+
+
+def _nll_ws(n, C_, dev):
+    nbytes = _lib.lib().stag_nll_workspace_bytes(n, C_)
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=dev), nbytes
+
+
+class _CategoricalNll(torch.autograd.Function):
+    """mean over the masked rows of -Categorical(probs=probs).log_prob(y) (stag_nll_categorical_fwd / _bwd).  Saved:
+    probs, y, mask and the one-element denom — nothing [N, C]-sized besides the input."""
+
+    @staticmethod
+    def forward(ctx, probs, y, mask):
+        dev = _lib.require_device(probs, y, mask)
+        n, C_ = probs.shape
+        out = torch.empty(2, dtype=torch.float32, device=dev)     # value, denom
+        ws, nbytes = _nll_ws(n, C_, dev)
+        with _lib.on_device(dev):
+            rc = _lib.lib().stag_nll_categorical_fwd(_lib.ptr(probs), max(probs.stride(0), C_), n, C_, _lib.ptr(y),
+                                                     _lib.ptr(mask), _lib.ptr(out), out.data_ptr() + 4, _lib.ptr(ws),
+                                                     nbytes, _lib.stream_of(dev))
+        _lib.check(rc, "stag_nll_categorical_fwd")
+        ctx.save_for_backward(probs, y, mask, out)
+        return out[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        probs, y, mask, out = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        dev = probs.device
+        n, C_ = probs.shape
+        g = _f32c(g.reshape(1))
+        dprobs = torch.empty((n, C_), dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            rc = _lib.lib().stag_nll_categorical_bwd(_lib.ptr(probs), max(probs.stride(0), C_), n, C_, _lib.ptr(y),
+                                                     _lib.ptr(mask), _lib.ptr(g), out.data_ptr() + 4, _lib.ptr(dprobs),
+                                                     C_, _lib.stream_of(dev))
+        _lib.check(rc, "stag_nll_categorical_bwd")
+        return dprobs, None, None
+
+
+class _BernoulliNll(torch.autograd.Function):
+    """mean over the elements of the masked rows of -Bernoulli(probs=probs).log_prob(y) (stag_nll_bernoulli_fwd /
+    _bwd).  Saved: probs, y, mask and the one-element denom."""
+
+    @staticmethod
+    def forward(ctx, probs, y, mask):
+        dev = _lib.require_device(probs, y, mask)
+        n, C_ = probs.shape
+        out = torch.empty(2, dtype=torch.float32, device=dev)     # value, denom
+        ws, nbytes = _nll_ws(n, C_, dev)
+        with _lib.on_device(dev):
+            rc = _lib.lib().stag_nll_bernoulli_fwd(_lib.ptr(probs), max(probs.stride(0), C_), _lib.ptr(y),
+                                                   max(y.stride(0), C_), n, C_, _lib.ptr(mask), _lib.ptr(out),
+                                                   out.data_ptr() + 4, _lib.ptr(ws), nbytes, _lib.stream_of(dev))
+        _lib.check(rc, "stag_nll_bernoulli_fwd")
+        ctx.save_for_backward(probs, y, mask, out)
+        return out[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        probs, y, mask, out = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        dev = probs.device
+        n, C_ = probs.shape
+        g = _f32c(g.reshape(1))
+        dprobs = torch.empty((n, C_), dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            rc = _lib.lib().stag_nll_bernoulli_bwd(_lib.ptr(probs), max(probs.stride(0), C_), _lib.ptr(y),
+                                                   max(y.stride(0), C_), n, C_, _lib.ptr(mask), _lib.ptr(g),
+                                                   out.data_ptr() + 4, _lib.ptr(dprobs), C_, _lib.stream_of(dev))
+        _lib.check(rc, "stag_nll_bernoulli_bwd")
+        return dprobs, None, None
+
+
+def nll_mean(likelihood, feat, y, mask=None):
+    """_masked_mean(-likelihood.log_prob(feat, y), mask) for a CategoricalLikelihood (y int64 [N]) or a
+    BernoulliLikelihood (y fp32 [N, C]) on device probabilities feat [N, C]; mask None or bool [N] (on the host: moved).
+    No masked row gives NaN, as the mean of nothing.  nll_why_not says when Likelihood.mean_nll takes it."""
+    why = _nll_form_why_not(likelihood, feat, y, mask)
+    if why is not None:
+        raise ValueError(f"nll_mean: no fused form ({why})")
+    if mask is not None:
+        if mask.device != feat.device:
+            mask = mask.to(feat.device)
+        mask = mask.contiguous()
+    if _nll_kind(likelihood) == "categorical":
+        return _CategoricalNll.apply(feat, y.contiguous(), mask)
+    return _BernoulliNll.apply(feat, y, mask)
+
+
 # ---- the sample-based KL fallback against a mixture prior (stag/layers.py:141-143) -----------------------------------
 # stag_sample_kl | the composed route (EdgeNoise.materialize(), both log_probs as eager torch over [E, Dn] and, for the
 # mixture, [E, Dn, K]).  The value is the same within tolerance either way: a speed and memory decision only.  True
